@@ -14,7 +14,14 @@ two launches (csrc/p2c_train.hip); the trainer captures it, verifies that the ca
 of its one recorded C-ABI call, and then replays the step by making that call (config.direct_replay: a graph launch costs
 ~5 us of start-up per replay).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+Prints ONE JSON line (rank 0) with the driver's contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step =
+the wall time of the K timed steps / K) and the workload's config. A plain run does only that: set-up, W warm-up steps, the K
+timed steps, the line.
+  --dump-outputs DIR  after the timed steps, what the last of them left for its caller, as float32 DIR/<name>.npy: loss (the
+                      value train_step returned), params (the flat parameter vector after the step's AdamW update), optim_exp_avg /
+                      optim_exp_avg_sq / optim_step (the optimizer state). Inputs are seeded: the same arguments give the same
+                      inputs in every run, so two builds can be compared output for output.
+  --full       adds everything below to the line (about a minute more on one GPU):
   repeat_ms_per_step  p50 / min / max of five more timed blocks of K steps (one hiccup cannot move the headline unseen)
   fresh_batch_ms_per_step  the same step fed a NEW batch object every iteration: staging copy + batch-start hook + replay
   step_breakdown_us  device time of every launch of the step at the benchmark batch (graph-timed, HIP events)
@@ -62,11 +69,14 @@ def parse():
     p.add_argument('--batch-size', type=int, default=256, help='clips per GPU')
     p.add_argument('--no-graph', action='store_true', help='eager launches instead of HIP-graph replay')
     p.add_argument('--full-outputs', action='store_true', help='materialise the logging tensors in training_step')
-    p.add_argument('--no-cpu-baseline', action='store_true')
-    p.add_argument('--no-sweep', action='store_true')
+    p.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy')
+    p.add_argument('--full', action='store_true', help='also the evidence beside the headline: repeat blocks, fresh-batch '
+                   'step, per-launch breakdown and roofline, sweeps, extra configs, CPU baseline')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='with --full')
+    p.add_argument('--no-sweep', action='store_true', help='with --full')
     p.add_argument('--cpu-seconds', type=float, default=12.0)
-    p.add_argument('--no-extra-configs', action='store_true')
-    p.add_argument('--repeats', type=int, default=5)
+    p.add_argument('--no-extra-configs', action='store_true', help='with --full')
+    p.add_argument('--repeats', type=int, default=5, help='with --full')
     return p.parse_args()
 
 
@@ -545,6 +555,19 @@ def timed_steps(trainer, flow, batches, steps, barrier):
     return time.perf_counter() - t0, loss
 
 
+def dump_outputs(out_dir, trainer, loss):
+    """--dump-outputs: what the last timed step left for its caller, float32, one DIR/<name>.npy each: the loss train_step
+    returned, the flat parameter vector after the step's update and the optimizer's state (a few hundred KB in all)."""
+    import numpy as np
+    arrays = {'loss': loss, 'params': trainer.flat.flat_param}
+    for o in trainer.optimizers:
+        for st in o.state.values():
+            arrays.update({f'optim_{k}': v for k, v in st.items() if isinstance(v, torch.Tensor) and v.is_floating_point()})
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().cpu().numpy())
+
+
 def extra_config(device, name, steps=100, warmup=10):
     """One more BASELINE.json configuration on this GPU: ms/step and clips/s of its captured train step (resident batch)."""
     from pedestrians_video_2_carla_amd.data.carla.carla_recorded_synthetic import SyntheticCarlaRecordedDataModule
@@ -742,26 +765,29 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     final_loss = float(loss)
+    if args.dump_outputs and rank == 0:       # before --full's measurements, which go on training
+        dump_outputs(args.dump_outputs, trainer, loss)
 
-    # more timed blocks of the same K steps, and the same step on a NEW batch object every iteration (every rank runs them:
-    # with an exchange in the step the collectives must pair up)
-    repeats = [timed_steps(trainer, flow, [batch], args.steps, barrier)[0] / args.steps * 1e3 for _ in range(max(args.repeats, 0))]
-    fresh = [dm.generate_batch(device, seed_offset=rank + 1000 * (k + 1)) for k in range(8)]
-    timed_steps(trainer, flow, fresh, 16, barrier)
-    fresh_ms = timed_steps(trainer, flow, fresh, args.steps, barrier)[0] / args.steps * 1e3
-    allreduce_us = None
-    if world > 1:
-        # the collective alone, event-timed on the step's stream: what the step pays for the exchange on top of its kernels
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for _ in range(5):
-            trainer.exchange.all_reduce_gradients()
-        e0.record()
-        for _ in range(50):
-            trainer.exchange.all_reduce_gradients()
-        e1.record()
-        e1.synchronize()
-        allreduce_us = e0.elapsed_time(e1) * 1e3 / 50
-        trainer.flat.zero_grad()
+    repeats, fresh_ms, allreduce_us = [], None, None
+    if args.full:
+        # more timed blocks of the same K steps, and the same step on a NEW batch object every iteration (every rank runs them:
+        # with an exchange in the step the collectives must pair up)
+        repeats = [timed_steps(trainer, flow, [batch], args.steps, barrier)[0] / args.steps * 1e3 for _ in range(max(args.repeats, 0))]
+        fresh = [dm.generate_batch(device, seed_offset=rank + 1000 * (k + 1)) for k in range(8)]
+        timed_steps(trainer, flow, fresh, 16, barrier)
+        fresh_ms = timed_steps(trainer, flow, fresh, args.steps, barrier)[0] / args.steps * 1e3
+        if world > 1:
+            # the collective alone, event-timed on the step's stream: what the step pays for the exchange on top of its kernels
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for _ in range(5):
+                trainer.exchange.all_reduce_gradients()
+            e0.record()
+            for _ in range(50):
+                trainer.exchange.all_reduce_gradients()
+            e1.record()
+            e1.synchronize()
+            allreduce_us = e0.elapsed_time(e1) * 1e3 / 50
+            trainer.flat.zero_grad()
 
     if rank != 0:
         if world > 1:
@@ -795,10 +821,27 @@ def main():
     if repeats:
         result['repeat_ms_per_step'] = {'n': len(repeats), 'p50': round(statistics.median(repeats), 4),
                                         'min': round(min(repeats), 4), 'max': round(max(repeats), 4)}
-    result['fresh_batch_ms_per_step'] = round(fresh_ms, 4)
+    if fresh_ms is not None:
+        result['fresh_batch_ms_per_step'] = round(fresh_ms, 4)
     if allreduce_us is not None:
         result['allreduce_us'] = round(allreduce_us, 2)
+    if args.full:
+        full_evidence(args, device, world, flow, trainer, batch, result)
+    print(json.dumps(result), flush=True)
+    if world > 1:
+        # every rank has finished; leave WITHOUT tearing the communicator down: destroy_process_group with a captured graph that
+        # holds the collective aborted the interpreter once in a while inside RCCL's teardown (tests/test_ddp_gpu.py), and a rank
+        # that dies after the line is printed would still fail the launcher
+        dist.barrier()
+        torch.cuda.synchronize()
+        sys.stdout.flush()
+        sys.stderr.flush()
+        os._exit(0)
 
+
+def full_evidence(args, device, world, flow, trainer, batch, result):
+    """--full, rank 0: the step's launches one by one and the roofline of the dominant one, the pose-head and whole-step sweeps,
+    the other BASELINE.json configs and the CPU baseline, added to `result`. (The optimizer really steps in here.)"""
     traffic = load_traffic()
     B = args.batch_size
 
@@ -865,16 +908,6 @@ def main():
         result['extra_configs'] = extra
     if not args.no_cpu_baseline and world == 1:
         result['cpu_baseline'] = cpu_baseline(args.batch_size, args.cpu_seconds)
-    print(json.dumps(result), flush=True)
-    if world > 1:
-        # every rank has finished; leave WITHOUT tearing the communicator down: destroy_process_group with a captured graph that
-        # holds the collective aborted the interpreter once in a while inside RCCL's teardown (tests/test_ddp_gpu.py), and a rank
-        # that dies after the line is printed would still fail the launcher
-        dist.barrier()
-        torch.cuda.synchronize()
-        sys.stdout.flush()
-        sys.stderr.flush()
-        os._exit(0)
 
 
 if __name__ == '__main__':

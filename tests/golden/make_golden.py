@@ -577,6 +577,41 @@ def golden_models_extra():
         npz('model_' + name, frames=frames, n_params=sum(p.numel() for p in model.parameters()), **outs, **sd)
 
 
+def golden_models_fp64():
+    """model_fp64.npz: the reference's LinearAE (three output types) and LinearAEResidual(+Leaky) run in float64 on the frames and
+    state_dicts of the fp32 fixtures model_linear_ae_*.npz. An fp32 forward rounds these outputs by ~1e-5, and how depends on the
+    summation order the host's GEMM kernels choose; the float64 outputs pin the function itself, whatever the host."""
+    if not os.path.isdir(REF_SRC):
+        sys.exit('reference tree not present: the committed .npz files are the artefact to use')
+    install_standins()
+    sys.path.insert(0, REF_SRC)
+    from pedestrians_video_2_carla.data.carla.skeleton import CARLA_SKELETON
+    from pedestrians_video_2_carla.modules.flow.output_types import MovementsModelOutputType as MT
+    from pedestrians_video_2_carla.modules.movements.linear_ae.linear_ae import LinearAE
+    from pedestrians_video_2_carla.modules.movements.linear_ae.linear_ae_residual import LinearAEResidual
+    from pedestrians_video_2_carla.modules.movements.linear_ae.linear_ae_residual_leaky import LinearAEResidualLeaky
+    outs = {}
+    for name, cls, kw in (
+            ('linear_ae_pose_changes', LinearAE, dict(movements_output_type=MT.pose_changes)),
+            ('linear_ae_absolute_loc', LinearAE, dict(movements_output_type=MT.absolute_loc)),
+            ('linear_ae_pose_2d', LinearAE, dict(movements_output_type=MT.pose_2d)),
+            ('linear_ae_residual', LinearAEResidual, {}),
+            ('linear_ae_residual_leaky', LinearAEResidualLeaky, dict(linear_size=64)),
+    ):
+        g = np.load(os.path.join(HERE, 'model_' + name + '.npz'))
+        model = cls(input_nodes=CARLA_SKELETON, output_nodes=CARLA_SKELETON, **kw).eval()
+        model.load_state_dict({k[4:]: torch.from_numpy(g[k]) for k in g.files if k.startswith('sd__')})
+        model.double()
+        with torch.no_grad():
+            out = model(torch.from_numpy(g['frames']).double())
+        if isinstance(out, torch.Tensor):
+            outs[name + '__out'] = out
+        else:
+            outs[name + '__out_loc'], outs[name + '__out_rot'] = out
+    assert all(v.dtype == torch.float64 for v in outs.values())
+    npz('model_fp64', **outs)
+
+
 def golden_seq2seq_h128():
     """model_seq2seq_embeddings_h128_pose_changes.npz: the reference's Seq2SeqEmbeddings at the hidden size its own configs use
     (configs/compare/carla-recorded_autoencoder_tests.yaml:38: hidden_size 128) with the pose_changes output (156 features per frame,
@@ -770,6 +805,8 @@ if __name__ == '__main__':
         golden_metrics_extra()
     elif sys.argv[1:] == ['models_extra']:
         golden_models_extra()
+    elif sys.argv[1:] == ['models_fp64']:
+        golden_models_fp64()
     elif sys.argv[1:] == ['seq2seq_h128']:
         golden_seq2seq_h128()
     elif sys.argv[1:] == ['losses_extra']:

@@ -6,9 +6,9 @@ set -o pipefail
 OUT=${1:-gpurun_out/r04}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 1
+python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 1
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_stats" -- python3 bench.py --no-extra-configs --no-cpu-baseline > "$OUT/bench_stats.log" 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_stats" -- python3 bench.py --full --no-extra-configs --no-cpu-baseline > "$OUT/bench_stats.log" 2>&1 || exit 1
 echo "stats done"
 for B in 256 1024 8192; do
   for C in FETCH_SIZE WRITE_SIZE; do
