@@ -347,6 +347,17 @@ typedef struct p2c_lstm_desc {
 P2C_API int p2c_lstm_rec_fwd(const p2c_lstm_desc *desc, void *stream);
 P2C_API int p2c_lstm_rec_bwd(const p2c_lstm_desc *desc, void *stream);
 
+/* ---- LSTM recurrence for any hidden size (K18) ------------------------------------------------------------------------------
+ * The same layer recurrence as p2c_lstm_rec_fwd / _bwd on the same descriptor, for any 1 <= H <= 1024 (no alignment or multiple
+ * of H required), as ONE LAUNCH PER TIME STEP: the launch boundary is the synchronisation between steps. Forward: T launches; it
+ * needs acts and cs (cs carries the cell state from one step to the next). Backward: T launches plus one for g_h0 when it is
+ * asked for; `workspace` holds p2c_lstm_steps_workspace_floats(B, H) floats (the carried d c; may be NULL when T <= 1), nothing
+ * in it is read before the call has written it. B <= 2^20; offsets are 64-bit. gx_bt, g_gx_bt and the dropout fields
+ * (out_drop, drop_state) are not implemented here: a descriptor that sets any of them is refused (P2C_E_SHAPE). */
+P2C_API int64_t p2c_lstm_steps_workspace_floats(int32_t B, int32_t H);
+P2C_API int p2c_lstm_steps_fwd(const p2c_lstm_desc *desc, void *stream);
+P2C_API int p2c_lstm_steps_bwd(const p2c_lstm_desc *desc, float *workspace, void *stream);
+
 /* ---- Seq2Seq decoder loop (K7c) -----------------------------------------------------------------------------------------
  * for t in range(T): out_t = fc(LSTM_2layers(x_t; encoder state)); x_{t+1} = out_t   (reference seq2seq.py:245-349; the
  * decoder state is NOT carried between frames, 272-288). The caller provides the frame-invariant recurrent terms

@@ -145,6 +145,9 @@ SYMBOLS = {
     'p2c_collate_fwd': (ctypes.c_int, [ctypes.POINTER(CollateDesc), _vp]),
     'p2c_lstm_rec_fwd': (ctypes.c_int, [ctypes.POINTER(LstmDesc), _vp]),
     'p2c_lstm_rec_bwd': (ctypes.c_int, [ctypes.POINTER(LstmDesc), _vp]),
+    'p2c_lstm_steps_workspace_floats': (_i64, [_i32, _i32]),
+    'p2c_lstm_steps_fwd': (ctypes.c_int, [ctypes.POINTER(LstmDesc), _vp]),
+    'p2c_lstm_steps_bwd': (ctypes.c_int, [ctypes.POINTER(LstmDesc), _vp, _vp]),
     'p2c_decoder_fwd': (ctypes.c_int, [ctypes.POINTER(DecoderDesc), _vp]),
     'p2c_decoder_bwd': (ctypes.c_int, [ctypes.POINTER(DecoderDesc), _vp]),
     'p2c_eval_workspace_floats': (_i64, [_i64]),

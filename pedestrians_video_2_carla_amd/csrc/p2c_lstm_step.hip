@@ -1,0 +1,298 @@
+// p2c_lstm_step.hip -- K18: the recurrent half of an LSTM layer for ANY hidden size (1 <= H <= 1024), one launch per time step
+// (gfx950, fp32 MFMA).
+//
+// K7b (p2c_lstm.hip) keeps W_hh in registers for the whole sequence: H / 16 waves of H VGPRs each, which stops at H = 128
+// (from H = 256 on the whole W_hh, 4H x H fp32, is larger than a CU's register file and LDS together). The reference's LSTM
+// movements model draws H from 64 ... 512 as any integer. Here the time loop is cut at its all-to-all seam instead: h[t] of every
+// unit feeds every gate of step t + 1, so each step is one launch and the launch boundary is the synchronisation between steps
+// (no waits between workgroups, no grid barrier).
+//
+// Forward, step t: gates = gx[t] (+ bias_a + bias_b) + h[t-1] W_hh^T, then c[t] = f c[t-1] + i g, h[t] = o tanh(c[t]) (gate order
+// i, f, g, o). A workgroup owns BM sequences x 16 hidden units with all four gates of those units: wave w takes sequences
+// [16w, 16w + 16) of the tile, the 4 x 16 rows {qH + u} of W_hh and the tile's h[t-1] rows are staged through LDS in K-chunks of
+// KC (zero-padded past H), and four v_mfma_f32_16x16x4f32 accumulators -- one per gate, started from gx[t] -- leave lane (c, g)
+// holding i, f, g, o of (sequence c, units 4g .. 4g + 3): the cell update happens in registers, as in K7b. h[t-1] is out[t-1]
+// (or h0), c[t-1] is cs[t-1] (or c0): the saved tensors carry the state from one launch to the next.
+// Backward, step t (descending): dh = g_out[t] (+ g_hT at T - 1) + dgates[t+1] W_hh[:, units] (K = 4H, staged the same way), then
+// the cell backward with the carried dc, read and written through a (B, H) workspace that only the owning lane touches; it writes
+// g_gx[t] (= d gates) and dc for step t - 1 (g_c0 at t = 0). One more launch forms g_h0 = dgates[0] W_hh. The weight gradients
+// are the caller's (dW_hh = sum_t dgates[t]^T h[t-1], one K12 launch over all (t, b)).
+// Addresses are 64-bit; rows past B / H are range-checked (loads give 0, stores are skipped). The staging loads of a chunk are all
+// issued first, unconditionally, from clamped (always valid) addresses, and the zero padding is a select on the LDS write: loads
+// under per-element branches were waited for one by one (measured: 107 / 221 us per forward / backward step at B = 256, H = 512).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/p2c.h"
+#include "p2c_rec_dev.h"
+
+namespace p2c_lstm_step {
+
+using namespace p2c_rec;
+constexpr int BM = 32;            // sequences per workgroup (16 per wave)
+constexpr int NT = 64 * BM / 16;  // threads per workgroup
+constexpr int KC = 64;            // K chunk staged in LDS
+constexpr int KP = KC + 4;        // LDS pitch: the 16 rows x 4 k of a fragment read fall in distinct banks (two passes)
+
+// a value loaded from global memory made resident here: the load cannot be sunk under the select that follows (a load under a
+// branch makes the compiler wait for each one at the join)
+__device__ __forceinline__ void pin1(float &v) { asm volatile("" : "+v"(v)); }
+
+struct Args {
+  const float *gx, *h0, *c0, *w_hh, *bias_a, *bias_b;
+  float *out, *hT, *cT, *acts, *cs;
+  const float *g_out, *g_hT, *g_cT;
+  float *g_gx, *g_h0, *g_c0, *dc;
+  int32_t T, B, H;
+};
+
+// ---- forward ----------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(NT) void lstm_step_fwd_kernel(const Args a, const int t) {
+  __shared__ float wl[64 * KP];   // rows q * 16 + i: W_hh row q H + ub + i, columns k0 .. k0 + KC
+  __shared__ float hl[BM * KP];   // rows s: h[t-1] of sequence b0 + s
+  const int H = a.H, B = a.B, T = a.T;
+  const int64_t G = 4 * (int64_t)H;
+  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4, w = threadIdx.x >> 6;
+  const int b0 = blockIdx.x * BM, ub = blockIdx.y * 16;
+  const int b = b0 + w * 16 + c, u0 = ub + 4 * g;         // this lane: sequence b, units u0 .. u0 + 3
+  const bool bok = b < B;
+
+  const float *cprev = t > 0 ? a.cs + ((int64_t)(t - 1) * B) * H : a.c0;
+  // per-lane rows: unconditional loads from clamped addresses (one round trip for all of them), then selects
+  const int bc = min(b, B - 1);
+  f32x4 acc[4], cp;
+  {
+    const float *gxr = a.gx + ((int64_t)t * B + bc) * G;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int uc = min(u0 + r, H - 1);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q][r] = gxr[q * H + uc];
+      cp[r] = cprev ? cprev[(int64_t)bc * H + uc] : 0.f;
+    }
+    if (a.bias_a || a.bias_b) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int uc = min(u0 + r, H - 1);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q][r] += (a.bias_a ? a.bias_a[q * H + uc] : 0.f) + (a.bias_b ? a.bias_b[q * H + uc] : 0.f);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const bool ok = bok && u0 + r < H;           // (padding lanes: zero pre-activations, as the zero-padded operands give)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q][r] = ok ? acc[q][r] : 0.f;
+    }
+  }
+
+  const float *hp = t > 0 ? a.out + ((int64_t)(t - 1) * B) * H : a.h0;   // NULL at t = 0 with the zero state: no product
+  if (hp) {
+    for (int k0 = 0; k0 < H; k0 += KC) {
+      constexpr int NW_ = 64 * KC / NT, NH_ = BM * KC / NT;
+      float vw[NW_], vh[NH_];
+#pragma unroll
+      for (int j = 0; j < NW_; ++j) {
+        const int e = threadIdx.x + j * NT, row = e / KC, k = e % KC, u = ub + (row & 15), kk = k0 + k;
+        vw[j] = a.w_hh[((int64_t)(row >> 4) * H + min(u, H - 1)) * H + min(kk, H - 1)];
+      }
+#pragma unroll
+      for (int j = 0; j < NH_; ++j) {
+        const int e = threadIdx.x + j * NT, s = e / KC, k = e % KC, kk = k0 + k;
+        vh[j] = hp[(int64_t)min(b0 + s, B - 1) * H + min(kk, H - 1)];
+      }
+#pragma unroll
+      for (int j = 0; j < NW_; ++j) {
+        pin1(vw[j]);
+        const int e = threadIdx.x + j * NT, row = e / KC, k = e % KC, u = ub + (row & 15), kk = k0 + k;
+        wl[row * KP + k] = (u < H && kk < H) ? vw[j] : 0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < NH_; ++j) {
+        pin1(vh[j]);
+        const int e = threadIdx.x + j * NT, s = e / KC, k = e % KC, kk = k0 + k;
+        hl[s * KP + k] = (b0 + s < B && kk < H) ? vh[j] : 0.f;
+      }
+      __syncthreads();
+      const int nks = (min(KC, H - k0) + 3) / 4;            // k-steps that touch a real column (the rest of the chunk is 0)
+      const float *wa = wl + c * KP + g, *hb = hl + (w * 16 + c) * KP + g;
+      for (int ks = 0; ks < nks; ++ks) {
+        const float bv = hb[4 * ks];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[q * 16 * KP + 4 * ks], bv, acc[q], 0, 0, 0);
+      }
+      __syncthreads();                                      // the chunk has been read before the next one is staged
+    }
+  }
+
+  if (!bok) return;
+  const int64_t row1 = ((int64_t)t * B + b) * H, row4 = ((int64_t)t * B + b) * G;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int u = u0 + r;
+    if (u >= H) continue;
+    const float ai = sigmoidf_(acc[0][r]), af = sigmoidf_(acc[1][r]), ag = tanhf_(acc[2][r]), ao = sigmoidf_(acc[3][r]);
+    const float ig = ai * ag;
+    const float cn = af * cp[r] + ig;
+    const float h = ao * tanhf_(cn);
+    a.out[row1 + u] = h;
+    a.cs[row1 + u] = cn;
+    a.acts[row4 + u] = ai, a.acts[row4 + H + u] = af, a.acts[row4 + 2 * H + u] = ag, a.acts[row4 + 3 * H + u] = ao;
+    if (t == T - 1) {
+      if (a.hT) a.hT[(int64_t)b * H + u] = h;
+      if (a.cT) a.cT[(int64_t)b * H + u] = cn;
+    }
+  }
+}
+
+// ---- backward ---------------------------------------------------------------------------------------------------------------
+// t >= 0: step t of the backward; t = -1: g_h0 = dgates[0] W_hh only.
+__global__ __launch_bounds__(NT) void lstm_step_bwd_kernel(const Args a, const int t) {
+  __shared__ float wl[16 * KP];   // rows i: W_hh[k0 + k][ub + i] (the transposed column block of the tile's units)
+  __shared__ float gl[BM * KP];   // rows s: dgates[t+1] of sequence b0 + s
+  const int H = a.H, B = a.B, T = a.T;
+  const int64_t G = 4 * (int64_t)H;
+  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4, w = threadIdx.x >> 6;
+  const int b0 = blockIdx.x * BM, ub = blockIdx.y * 16;
+  const int b = b0 + w * 16 + c, u0 = ub + 4 * g;
+  const bool bok = b < B;
+
+  // the saved rows of the step: requested before the product, used after it
+  f32x4 ai, af, ag, ao, ct, cp, go, dc;
+  if (t >= 0) {   // unconditional loads from clamped addresses (lanes past B / H compute values that are never stored)
+    const int bc = min(b, B - 1);
+    const int64_t row1 = ((int64_t)t * B + bc) * H, row4 = ((int64_t)t * B + bc) * G;
+    const float *cprev = t > 0 ? a.cs + ((int64_t)(t - 1) * B) * H : a.c0;
+    const float *dcin = t == T - 1 ? a.g_cT : a.dc;          // the carry: g_cT at the last step, then what step t + 1 left
+    const float *ghT = t == T - 1 ? a.g_hT : nullptr;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int uc = min(u0 + r, H - 1);
+      ai[r] = a.acts[row4 + uc], af[r] = a.acts[row4 + H + uc], ag[r] = a.acts[row4 + 2 * H + uc], ao[r] = a.acts[row4 + 3 * H + uc];
+      ct[r] = a.cs[row1 + uc];
+      cp[r] = cprev ? cprev[(int64_t)bc * H + uc] : 0.f;
+      go[r] = a.g_out ? a.g_out[row1 + uc] : 0.f;
+      dc[r] = dcin ? dcin[(int64_t)bc * H + uc] : 0.f;
+    }
+    if (ghT) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) go[r] += ghT[(int64_t)bc * H + min(u0 + r, H - 1)];
+    }
+  }
+
+  // dh = dgates[t+1] W_hh[:, units]: four accumulators over the k-steps break the dependent MFMA chain
+  f32x4 e[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) e[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  if (t + 1 < T) {
+    const float *gn = a.g_gx + ((int64_t)(t + 1) * B) * G;
+    for (int64_t k0 = 0; k0 < G; k0 += KC) {
+      constexpr int NW_ = 16 * KC / NT, NG_ = BM * KC / NT;
+      float vw[NW_], vg[NG_];
+#pragma unroll
+      for (int j = 0; j < NW_; ++j) {
+        const int x = threadIdx.x + j * NT, k = x / 16, i = x % 16;
+        vw[j] = a.w_hh[min(k0 + k, G - 1) * H + min(ub + i, H - 1)];
+      }
+#pragma unroll
+      for (int j = 0; j < NG_; ++j) {
+        const int x = threadIdx.x + j * NT, s = x / KC, k = x % KC;
+        vg[j] = gn[(int64_t)min(b0 + s, B - 1) * G + min(k0 + k, G - 1)];
+      }
+#pragma unroll
+      for (int j = 0; j < NW_; ++j) {
+        pin1(vw[j]);
+        const int x = threadIdx.x + j * NT, k = x / 16, i = x % 16;
+        wl[i * KP + k] = (ub + i < H && k0 + k < G) ? vw[j] : 0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < NG_; ++j) {
+        pin1(vg[j]);
+        const int x = threadIdx.x + j * NT, s = x / KC, k = x % KC;
+        gl[s * KP + k] = (b0 + s < B && k0 + k < G) ? vg[j] : 0.f;
+      }
+      __syncthreads();
+      const int n16 = (int)((min((int64_t)KC, G - k0) + 15) / 16);   // groups of four k-steps that touch a real row of W_hh
+      const float *wa = wl + c * KP + g, *gb = gl + (w * 16 + c) * KP + g;
+      for (int j = 0; j < n16; ++j) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) e[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[16 * j + 4 * q], gb[16 * j + 4 * q], e[q], 0, 0, 0);
+      }
+      __syncthreads();
+    }
+  }
+  const f32x4 dhr = (e[0] + e[1]) + (e[2] + e[3]);
+  if (!bok) return;
+
+  if (t < 0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (u0 + r < H) a.g_h0[(int64_t)b * H + u0 + r] = dhr[r];
+    return;
+  }
+  const int64_t row4 = ((int64_t)t * B + b) * G;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int u = u0 + r;
+    if (u >= H) continue;
+    const float dht = go[r] + dhr[r];
+    const float tc = tanhf_(ct[r]);
+    const float dct = dc[r] + dht * ao[r] * (1.f - tc * tc);
+    const float po = dht * tc * ao[r] * (1.f - ao[r]);
+    const float pi = dct * ag[r] * ai[r] * (1.f - ai[r]);
+    const float pf = dct * cp[r] * af[r] * (1.f - af[r]);
+    const float pg = dct * ai[r] * (1.f - ag[r] * ag[r]);
+    a.g_gx[row4 + u] = pi, a.g_gx[row4 + H + u] = pf, a.g_gx[row4 + 2 * H + u] = pg, a.g_gx[row4 + 3 * H + u] = po;
+    const float dcn = dct * af[r];
+    if (t > 0) a.dc[(int64_t)b * H + u] = dcn;
+    else if (a.g_c0) a.g_c0[(int64_t)b * H + u] = dcn;
+  }
+}
+
+}  // namespace p2c_lstm_step
+
+using namespace p2c_lstm_step;
+
+static int check_steps(const p2c_lstm_desc *d, Args &a) {
+  if (!d || !d->w_hh) return P2C_E_NULL;
+  if (d->T < 0 || d->B < 0 || d->B > (1 << 20) || d->H < 1 || d->H > 1024) return P2C_E_SHAPE;
+  // fields this form does not implement are refused, not ignored
+  if (d->gx_bt || d->g_gx_bt || d->out_drop || d->drop_state) return P2C_E_SHAPE;
+  a = Args{};
+  a.gx = d->gx, a.h0 = d->h0, a.c0 = d->c0, a.w_hh = d->w_hh, a.bias_a = d->bias_a, a.bias_b = d->bias_b;
+  a.out = d->out, a.hT = d->hT, a.cT = d->cT, a.acts = d->acts, a.cs = d->cs;
+  a.g_out = d->g_out, a.g_hT = d->g_hT, a.g_cT = d->g_cT, a.g_gx = d->g_gx, a.g_h0 = d->g_h0, a.g_c0 = d->g_c0;
+  a.T = d->T, a.B = d->B, a.H = d->H;
+  return 0;
+}
+
+static dim3 steps_grid(const Args &a) { return dim3((unsigned)((a.B + BM - 1) / BM), (unsigned)((a.H + 15) / 16)); }
+
+extern "C" int64_t p2c_lstm_steps_workspace_floats(int32_t B, int32_t H) {
+  return (B < 0 || H < 0) ? 0 : (int64_t)B * H;
+}
+
+extern "C" int p2c_lstm_steps_fwd(const p2c_lstm_desc *d, void *stream) {
+  Args a;
+  int rc = check_steps(d, a);
+  if (rc) return rc;
+  if (!a.gx || !a.out || !a.acts || !a.cs) return P2C_E_NULL;   // cs carries the cell state from one launch to the next
+  if (a.B == 0) return 0;
+  for (int t = 0; t < a.T; ++t) hipLaunchKernelGGL(lstm_step_fwd_kernel, steps_grid(a), dim3(NT), 0, (hipStream_t)stream, a, t);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+extern "C" int p2c_lstm_steps_bwd(const p2c_lstm_desc *d, float *workspace, void *stream) {
+  Args a;
+  int rc = check_steps(d, a);
+  if (rc) return rc;
+  if (!a.acts || !a.cs || !a.g_gx) return P2C_E_NULL;
+  if (a.T > 1 && !workspace) return P2C_E_NULL;
+  a.dc = workspace;
+  if (a.B == 0 || a.T == 0) return 0;
+  for (int t = a.T - 1; t >= 0; --t) hipLaunchKernelGGL(lstm_step_bwd_kernel, steps_grid(a), dim3(NT), 0, (hipStream_t)stream, a, t);
+  if (a.g_h0) hipLaunchKernelGGL(lstm_step_bwd_kernel, steps_grid(a), dim3(NT), 0, (hipStream_t)stream, a, -1);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}

@@ -1,0 +1,1 @@
+from .lstm import LSTM  # noqa: F401

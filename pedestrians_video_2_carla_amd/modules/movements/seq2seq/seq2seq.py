@@ -47,16 +47,17 @@ def _fused_ok(rnn, x) -> bool:
 _WARNED = set()
 
 
-def _warn_fallback(rnn):
+def _warn_fallback(rnn, who='Seq2Seq', covers='hidden sizes 16 / 32 / 48 / 64 / 96 / 128, no projection'):
     """Once per shape: an fp32 LSTM stack on the GPU that the HIP recurrence does not cover runs through the framework's RNN
     (MIOpen: about 15x slower per step at cfg3's sizes) -- e.g. the reference's own ``hidden_size: 128`` configs
-    (configs/compare/carla-recorded_autoencoder_tests.yaml:38). Not silent."""
-    key = (rnn.hidden_size, rnn.proj_size)
+    (configs/compare/carla-recorded_autoencoder_tests.yaml:38). Not silent. ``who`` / ``covers``: the model that falls back and
+    the widths its HIP path takes (the LSTM movements model: any hidden size up to 1024)."""
+    key = (rnn.hidden_size, rnn.proj_size) if who == 'Seq2Seq' else (who, rnn.hidden_size, rnn.proj_size)
     if key in _WARNED:
         return
     _WARNED.add(key)
-    warnings.warn(f'Seq2Seq: nn.LSTM(hidden_size={rnn.hidden_size}, proj_size={rnn.proj_size}) is outside the HIP recurrence '
-                  f'(hidden sizes 16 / 32 / 48 / 64 / 96 / 128, no projection): this stack runs on the framework RNN path, roughly an order of '
+    warnings.warn(f'{who}: nn.LSTM(hidden_size={rnn.hidden_size}, proj_size={rnn.proj_size}) is outside the HIP recurrence '
+                  f'({covers}): this stack runs on the framework RNN path, roughly an order of '
                   f'magnitude slower per step', RuntimeWarning, stacklevel=3)
 
 

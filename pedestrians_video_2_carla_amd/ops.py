@@ -996,10 +996,18 @@ def kernel_dropout_enabled() -> bool:
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# LSTM layer: library GEMM for the input projection + one HIP launch for the recurrence (K7b)
+# LSTM layer: library GEMM for the input projection + one HIP launch for the recurrence (K7b), or one launch per time step
+# for any other hidden size up to 1024 (K18)
 # ----------------------------------------------------------------------------------------------------------------------
 def lstm_supported(hidden_size: int) -> bool:
+    """The widths of the single-launch recurrence (K7b). Gates Seq2Seq's encoder stack and decoder loop."""
     return hidden_size in (16, 32, 48, 64, 96, 128)
+
+
+def lstm_steps_supported(hidden_size: int) -> bool:
+    """The widths of the one-launch-per-step recurrence (K18, p2c_lstm_steps_*): any 1 <= H <= 1024. ``lstm_layer`` takes it
+    for every width outside ``lstm_supported``."""
+    return 1 <= hidden_size <= 1024
 
 
 class LSTMRecurrenceFunction(torch.autograd.Function):
@@ -1019,8 +1027,10 @@ class LSTMRecurrenceFunction(torch.autograd.Function):
             h0, c0 = _require_device(h0, 'h0'), _require_device(c0, 'c0')
         if G != 4 * H or w_hh.shape[0] != 4 * H or (not ctx.zero_state and (h0.shape != (B, H) or c0.shape != (B, H))):
             raise RuntimeError(f'inconsistent LSTM shapes: gx {tuple(gx.shape)}, w_hh {tuple(w_hh.shape)}, h0 {tuple(h0.shape)}')
-        if not lstm_supported(H):
-            raise RuntimeError(f'hidden size {H} is not supported by the HIP recurrence (16, 32, 48 or 64)')
+        ctx.steps = not lstm_supported(H)                     # K18 for the widths K7b does not cover
+        if ctx.steps and not lstm_steps_supported(H):
+            raise RuntimeError(f'hidden size {H} is not supported by the HIP recurrence (16, 32, 48, 64, 96, 128 in one launch, '
+                               f'any other 1 ... 1024 one launch per step)')
         f32 = dict(dtype=torch.float32, device=gx.device)
         out, hT, cT = torch.empty(T, B, H, **f32), torch.empty(B, H, **f32), torch.empty(B, H, **f32)
         acts, cs = torch.empty(T, B, 4 * H, **f32), torch.empty(T, B, H, **f32)
@@ -1031,7 +1041,10 @@ class LSTMRecurrenceFunction(torch.autograd.Function):
             d.h0, d.c0 = h0.data_ptr(), c0.data_ptr()
         d.out, d.hT, d.cT, d.acts, d.cs = out.data_ptr(), hT.data_ptr(), cT.data_ptr(), acts.data_ptr(), cs.data_ptr()
         with torch.cuda.device(gx.device):
-            _lib.check(lib.p2c_lstm_rec_fwd(ctypes.byref(d), _stream()), 'p2c_lstm_rec_fwd')
+            if ctx.steps:
+                _lib.check(lib.p2c_lstm_steps_fwd(ctypes.byref(d), _stream()), 'p2c_lstm_steps_fwd')
+            else:
+                _lib.check(lib.p2c_lstm_rec_fwd(ctypes.byref(d), _stream()), 'p2c_lstm_rec_fwd')
         ctx.save_for_backward(h0, c0, w_hh, out, acts, cs)
         return out, hT, cT
 
@@ -1055,7 +1068,11 @@ class LSTMRecurrenceFunction(torch.autograd.Function):
         d.g_cT = _ptr(None if g_cT is None else _require_device(g_cT, 'grad cT'))
         d.g_gx = g_gx.data_ptr()
         with torch.cuda.device(out.device):
-            _lib.check(lib.p2c_lstm_rec_bwd(ctypes.byref(d), _stream()), 'p2c_lstm_rec_bwd')
+            if ctx.steps:
+                ws = torch.empty(lib.p2c_lstm_steps_workspace_floats(B, H), **f32)
+                _lib.check(lib.p2c_lstm_steps_bwd(ctypes.byref(d), ws.data_ptr(), _stream()), 'p2c_lstm_steps_bwd')
+            else:
+                _lib.check(lib.p2c_lstm_rec_bwd(ctypes.byref(d), _stream()), 'p2c_lstm_rec_bwd')
         g_w = None
         if ctx.needs_input_grad[3]:       # dW_hh = sum_t dgates[t]^T h[t-1] over all (t, b) (K12)
             sink = _sink(w_hh)
@@ -1093,7 +1110,8 @@ def _prefer_rocblas_once():
 def lstm_layer(x: Tensor, h0: Optional[Tensor], c0: Optional[Tensor], w_ih: Tensor, w_hh: Tensor, b_ih: Optional[Tensor],
                b_hh: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
     """One unidirectional torch.nn.LSTM layer: x (T,B,I) -> (out (T,B,H), hT (B,H), cT (B,H)). The input projection for
-    all time steps is one dense GEMM (library); the time loop is one HIP launch (p2c_lstm_rec_fwd)."""
+    all time steps is one dense GEMM (library); the time loop is one HIP launch (p2c_lstm_rec_fwd) for the widths of
+    ``lstm_supported`` and one launch per time step (p2c_lstm_steps_fwd) for any other width up to 1024."""
     _prefer_rocblas_once()
     T, B, I = x.shape
     bias = None if b_ih is None else (b_ih + b_hh if b_hh is not None else b_ih)
