@@ -605,6 +605,37 @@ P2C_API int p2c_gemm_tn(const float *a, int64_t lda, const float *b, int64_t ldb
                 int32_t K, int32_t accumulate, const float *row_scale, int32_t rows_per_scale, float *bias_out,
                 float *workspace, void *stream);
 
+/* ---- BatchNorm1d + ReLU + dropout (+ residual) over a row-major (N, C) activation (K19) ------------------------------------------
+ * Forward: z = act(gamma (y - mean) rstd + beta) * keep(e) / (1 - p) [+ residual], act = ReLU when relu != 0, else identity.
+ *   training != 0: mean / rstd (C each) are the batch statistics (biased variance, rstd = 1 / sqrt(var + eps)), computed in a fixed
+ *   order (bitwise reproducible) and written for the backward; running_mean / running_var (both or neither) are updated in place
+ *   with `momentum` and the unbiased variance, as torch.nn.BatchNorm1d. Needs N >= 2 and `workspace`. Three launches.
+ *   training == 0: the running statistics (required), no dropout; mean / rstd receive running_mean and 1 / sqrt(running_var + eps)
+ *   for a backward; workspace may be NULL. One launch.
+ * Backward: g = g_z keep / (1 - p) [pre > 0]; g_beta = sum_rows g, g_gamma = sum_rows g (y - mean) rstd (stored, or added to when
+ *   accumulate != 0); g_y = gamma rstd (g - g_beta / N - (y - mean) rstd g_gamma / N) in training, gamma rstd g in eval (training
+ *   as in the forward call). The residual's gradient is g_z itself (the caller's). Same fixed order; three launches.
+ * Dropout (training only, drop_state != NULL and drop_p > 0): the hashed masks of the recurrence kernels, site drop_site of the
+ *   4-word state {seed_lo, seed_hi, step, next}; the forward reads `step` and leaves next = step + 1, the backward draws the
+ *   forward's masks from next - 1 and leaves step = next. No mask tensor.
+ * Element indices are 32-bit: N C >= 2^31 is refused (P2C_E_SHAPE) before anything is launched. workspace holds
+ * p2c_bnorm_workspace_floats(N, C) floats; nothing in it is read before the call has written it. */
+typedef struct p2c_bnorm_desc {
+  int64_t N;
+  int32_t C, training, relu, accumulate;
+  float eps, momentum;
+  const float *y, *gamma, *beta, *residual;    /* residual: NULL or (N, C) */
+  float *z, *mean, *rstd, *running_mean, *running_var;
+  const float *g_z;
+  float *g_y, *g_gamma, *g_beta;
+  void *drop_state;
+  float drop_p;
+  int32_t drop_site;
+} p2c_bnorm_desc;
+P2C_API int64_t p2c_bnorm_workspace_floats(int64_t N, int32_t C);
+P2C_API int p2c_bnorm_fwd(const p2c_bnorm_desc *desc, float *workspace, void *stream);
+P2C_API int p2c_bnorm_bwd(const p2c_bnorm_desc *desc, float *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

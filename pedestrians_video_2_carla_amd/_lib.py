@@ -84,6 +84,15 @@ class LstmDesc(ctypes.Structure):
                 ('out_drop', _f32p), ('drop_state', ctypes.c_void_p), ('drop_p', ctypes.c_float), ('drop_site', ctypes.c_int32)]
 
 
+class BnormDesc(ctypes.Structure):
+    """p2c_bnorm_desc (include/p2c.h)."""
+    _fields_ = [('N', _i64), ('C', _i32), ('training', _i32), ('relu', _i32), ('accumulate', _i32), ('eps', ctypes.c_float),
+                ('momentum', ctypes.c_float)] + [(n, _f32p) for n in ('y', 'gamma', 'beta', 'residual', 'z', 'mean', 'rstd',
+                                                                     'running_mean', 'running_var', 'g_z', 'g_y', 'g_gamma',
+                                                                     'g_beta')] + [
+        ('drop_state', ctypes.c_void_p), ('drop_p', ctypes.c_float), ('drop_site', _i32)]
+
+
 class DecoderDesc(ctypes.Structure):
     """p2c_decoder_desc (include/p2c.h)."""
     _fields_ = [('T', ctypes.c_int32), ('B', ctypes.c_int32), ('H', ctypes.c_int32), ('O', ctypes.c_int32)] + [
@@ -148,6 +157,9 @@ SYMBOLS = {
     'p2c_lstm_steps_workspace_floats': (_i64, [_i32, _i32]),
     'p2c_lstm_steps_fwd': (ctypes.c_int, [ctypes.POINTER(LstmDesc), _vp]),
     'p2c_lstm_steps_bwd': (ctypes.c_int, [ctypes.POINTER(LstmDesc), _vp, _vp]),
+    'p2c_bnorm_workspace_floats': (_i64, [_i64, _i32]),
+    'p2c_bnorm_fwd': (ctypes.c_int, [ctypes.POINTER(BnormDesc), _vp, _vp]),
+    'p2c_bnorm_bwd': (ctypes.c_int, [ctypes.POINTER(BnormDesc), _vp, _vp]),
     'p2c_decoder_fwd': (ctypes.c_int, [ctypes.POINTER(DecoderDesc), _vp]),
     'p2c_decoder_bwd': (ctypes.c_int, [ctypes.POINTER(DecoderDesc), _vp]),
     'p2c_eval_workspace_floats': (_i64, [_i64]),

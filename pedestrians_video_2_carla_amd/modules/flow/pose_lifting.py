@@ -21,6 +21,7 @@ from pedestrians_video_2_carla_amd.loss.fused import FusedLosses
 from pedestrians_video_2_carla_amd.modules.flow.base import LitBaseFlow
 from pedestrians_video_2_carla_amd.modules.flow.output_types import MovementsModelOutputType, TrajectoryModelOutputType
 from pedestrians_video_2_carla_amd.modules.layers.projection import ProjectionModule
+from pedestrians_video_2_carla_amd.modules.movements.baseline_3d_pose import Baseline3DPose, Baseline3DPoseRot
 from pedestrians_video_2_carla_amd.modules.movements.linear_ae import LinearAE, LinearAEResidual, LinearAEResidualLeaky
 from pedestrians_video_2_carla_amd.modules.movements.lstm import LSTM
 from pedestrians_video_2_carla_amd.modules.movements.seq2seq import (Seq2Seq, Seq2SeqEmbeddings, Seq2SeqResidualA, Seq2SeqResidualB,
@@ -57,7 +58,8 @@ class LitPoseLiftingFlow(LitBaseFlow):
         return {
             'movements': {m.__name__: m for m in [ZeroMovements, LinearAE, Seq2Seq, Seq2SeqEmbeddings, Seq2SeqResidualA,
                                                   Seq2SeqResidualB, Seq2SeqResidualC, LinearAEResidual,
-                                                  LinearAEResidualLeaky, PoseFormer, LSTM]},
+                                                  LinearAEResidualLeaky, PoseFormer, LSTM, Baseline3DPose,
+                                                  Baseline3DPoseRot]},
             'trajectory': {m.__name__: m for m in [ZeroTrajectory]},
         }
 

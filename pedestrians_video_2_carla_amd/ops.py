@@ -5,6 +5,7 @@ No CPU path: host tensors raise.
 """
 import ctypes
 import os
+import warnings
 import weakref
 from dataclasses import dataclass, field
 from typing import Dict, Optional, Sequence, Tuple
@@ -1805,6 +1806,109 @@ class LayerNormFunction(torch.autograd.Function):
 
 def layer_norm(x: Tensor, weight: Tensor, bias: Tensor, eps: float) -> Tensor:
     return LayerNormFunction.apply(x, weight, bias, eps)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# BatchNorm1d + ReLU + dropout (+ residual) over (N, C) rows (K19, csrc/p2c_bnorm.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+BNORM_MAX_ELEMENTS = 1 << 31        # the hashed dropout stream indexes elements with 32 bits
+_BN_WARNED = set()
+
+
+class BatchNormActFunction(torch.autograd.Function):
+    """z = relu(batch_norm(y)) * mask / (1 - p) [+ residual] for y (N, C): three launches forward in training (slab statistics,
+    their fixed-order combine + the running-statistics update, the element-wise pass), one in eval; three backward. Saved: y,
+    mean and rstd only -- the ReLU gate and the dropout mask (hashed, site ``site`` of ``drop_state``) are recomputed. Inside the
+    trainer's ``grad_sinks`` context the gamma / beta gradients are added straight into their ``.grad``."""
+
+    @staticmethod
+    def forward(ctx, y, weight, bias, residual, running_mean, running_var, training: bool, momentum: float, eps: float,
+                p: float, drop_state, site: int, relu: bool):
+        lib = _lib.lib()
+        N, C = y.shape
+        f32 = dict(dtype=torch.float32, device=y.device)
+        z, mean, rstd = torch.empty_like(y), torch.empty(C, **f32), torch.empty(C, **f32)
+        ws = torch.empty(max(1, lib.p2c_bnorm_workspace_floats(N, C)), **f32)
+        d = _lib.BnormDesc()
+        d.N, d.C, d.training, d.relu, d.eps, d.momentum = N, C, int(training), int(relu), float(eps), float(momentum)
+        d.y, d.gamma, d.beta, d.residual = y.data_ptr(), weight.data_ptr(), bias.data_ptr(), _ptr(residual)
+        d.z, d.mean, d.rstd = z.data_ptr(), mean.data_ptr(), rstd.data_ptr()
+        d.running_mean, d.running_var = _ptr(running_mean), _ptr(running_var)
+        use_drop = training and p > 0 and drop_state is not None
+        d.drop_state, d.drop_p, d.drop_site = (drop_state.data_ptr() if use_drop else None), float(p if use_drop else 0.), int(site)
+        with torch.cuda.device(y.device):
+            _lib.check(lib.p2c_bnorm_fwd(ctypes.byref(d), ws.data_ptr(), _stream()), 'p2c_bnorm_fwd')
+        ctx.save_for_backward(y, weight, bias, mean, rstd)
+        ctx.drop_state, ctx.cfg = (drop_state if use_drop else None), (bool(training), float(p if use_drop else 0.), int(site),
+                                                                         bool(relu), residual is not None)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        lib = _lib.lib()
+        y, weight, bias, mean, rstd = ctx.saved_tensors
+        training, p, site, relu, has_residual = ctx.cfg
+        N, C = y.shape
+        gz = _require_device(gz, 'grad')
+        gy = torch.empty_like(y)
+        sw, sb = _sink(weight), _sink(bias)
+        if sw is None or sb is None:
+            sw = sb = None
+        gw = sw if sw is not None else torch.empty_like(weight)
+        gb = sb if sb is not None else torch.empty_like(bias)
+        ws = torch.empty(max(1, lib.p2c_bnorm_workspace_floats(N, C)), dtype=torch.float32, device=y.device)
+        d = _lib.BnormDesc()
+        d.N, d.C, d.training, d.relu, d.accumulate = N, C, int(training), int(relu), int(sw is not None)
+        d.y, d.gamma, d.beta, d.mean, d.rstd = y.data_ptr(), weight.data_ptr(), bias.data_ptr(), mean.data_ptr(), rstd.data_ptr()
+        d.g_z, d.g_y, d.g_gamma, d.g_beta = gz.data_ptr(), gy.data_ptr(), gw.data_ptr(), gb.data_ptr()
+        d.drop_state, d.drop_p, d.drop_site = _ptr(ctx.drop_state), p, site
+        with torch.cuda.device(y.device):
+            _lib.check(lib.p2c_bnorm_bwd(ctypes.byref(d), ws.data_ptr(), _stream()), 'p2c_bnorm_bwd')
+        return (gy, None if sw is not None else gw, None if sb is not None else gb, gz if has_residual else None,
+                None, None, None, None, None, None, None, None, None)
+
+
+def batch_norm_act_supported(y: Tensor, bn: torch.nn.BatchNorm1d) -> bool:
+    """The inputs K19 covers: a contiguous fp32 (N, C) device tensor outside autocast, an affine BatchNorm1d that tracks running
+    statistics with a float momentum, and N C < 2^31 (N C beyond that takes the framework ops, with a warning)."""
+    if not (y.is_cuda and y.dtype == torch.float32 and y.ndim == 2 and y.is_contiguous() and not torch.is_autocast_enabled()
+            and isinstance(bn.momentum, float) and bn.track_running_stats and bn.affine and bn.weight.is_cuda
+            and bn.weight.dtype == torch.float32 and bn.running_mean is not None and y.shape[1] == bn.num_features):
+        return False
+    if y.shape[0] * y.shape[1] >= BNORM_MAX_ELEMENTS:
+        key = tuple(y.shape)
+        if key not in _BN_WARNED:
+            _BN_WARNED.add(key)
+            warnings.warn(f'batch_norm_act: {tuple(y.shape)} has 2^31 elements or more (the fused kernel indexes them with 32 bits): '
+                          f'this layer runs on the framework ops', RuntimeWarning, stacklevel=3)
+        return False
+    return True
+
+
+def batch_norm_act(y: Tensor, bn: torch.nn.BatchNorm1d, p: float, drop_state: Optional[Tensor], site: int,
+                   residual: Optional[Tensor] = None, relu: bool = True) -> Tensor:
+    """``dropout(relu(bn(y)), p) [+ residual]`` for 2-D y, with the BatchNorm1d module's own parameters and buffers (running
+    statistics and ``num_batches_tracked`` advance as in ``bn(y)``). On the device this is K19, whose dropout mask is drawn from
+    ``drop_state`` (``dropout_state``; ``site`` tells the layers that share it apart); ``drop_state=None`` with p > 0 -- the
+    framework's dropout asked for (P2C_TORCH_DROPOUT=1) -- and every input K19 does not cover take the framework ops."""
+    training = bn.training
+    kernel_drop = not (training and p > 0) or drop_state is not None
+    if kernel_drop and batch_norm_act_supported(y, bn):
+        if training and y.shape[0] < 2:
+            raise ValueError(f'Expected more than 1 value per channel when training, got input size {torch.Size(y.shape)}')
+        if residual is not None:
+            residual = residual.contiguous()
+        z = BatchNormActFunction.apply(y, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, training,
+                                       bn.momentum, bn.eps, float(p), drop_state, int(site), bool(relu))
+        if training:
+            bn.num_batches_tracked.add_(1)
+        return z
+    z = bn(y)
+    if relu:
+        z = torch.relu(z)
+    if training and p > 0:
+        z = torch.nn.functional.dropout(z, p, True)
+    return z if residual is None else z + residual
 
 
 # ----------------------------------------------------------------------------------------------------------------------
