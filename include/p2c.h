@@ -577,7 +577,7 @@ P2C_API int p2c_debug_poison_lds(void *stream);
  * Epilogue, in this order: v = acc + bias[n] (bias may be NULL); act = 1: aux_out[m][n] = v if aux_out != NULL, then
  * v = gelu(v) (erf form, torch.nn.GELU()); act = 2: v *= gelu'(aux[m][n]) (the backward through that activation, aux = the
  * stored pre-activation); v *= row_scale[m / rows_per_scale] if row_scale != NULL (per-sample stochastic-depth factor);
- * v += residual[m][n] if residual != NULL; C[m][n] = v. C may alias residual. fp32 in, fp32 accumulate (an fmaf chain in k
+ * act = 3 / 4: ReLU + dropout and their backward (below); v += residual[m][n] if residual != NULL; C[m][n] = v. C may alias residual. fp32 in, fp32 accumulate (an fmaf chain in k
  * order). 16-byte loads when every base / leading dimension allows, dword loads otherwise. Returns 0 or P2C_E_*. */
 typedef struct p2c_gemm_desc {
   int32_t M, N, K, trans_b;
@@ -589,6 +589,14 @@ typedef struct p2c_gemm_desc {
   const float *aux; float *aux_out; int64_t ldaux;
   const float *row_scale;
   const float *residual; int64_t ldr;
+  /* act 3 / 4 (nn.TransformerEncoderLayer's FFN): act 3: v = relu(v) keep(m N + n) / (1 - drop_p) with the hashed mask of site
+   * drop_site of drop_state (the 4-word stream of p2c_bnorm_desc: reads `step`, leaves next = step + 1; drop_state NULL: relu
+   * alone); act 4: v *= [aux[m][n] > 0] / (1 - drop_p), aux = act 3's output -- relu' and the kept mask in one test, so the
+   * backward needs neither the pre-activation nor a mask tensor. 0 <= drop_p < 1; act 3 with drop_state refuses M N >= 2^31
+   * (P2C_E_SHAPE, nothing launched). Zero for acts 0..2. */
+  void *drop_state;
+  float drop_p;
+  int32_t drop_site;
 } p2c_gemm_desc;
 P2C_API int p2c_gemm(const p2c_gemm_desc *desc, void *stream);
 /* The weight gradient of a WIDE dense layer, C (M, N) (+)= A^T B with A (K, M) and B (K, N) row-major over K = rows >> M, N
@@ -635,6 +643,34 @@ typedef struct p2c_bnorm_desc {
 P2C_API int64_t p2c_bnorm_workspace_floats(int64_t N, int32_t C);
 P2C_API int p2c_bnorm_fwd(const p2c_bnorm_desc *desc, float *workspace, void *stream);
 P2C_API int p2c_bnorm_bwd(const p2c_bnorm_desc *desc, float *workspace, void *stream);
+
+/* ---- the post-norm nn.TransformerEncoderLayer of SimpleTransformer (K20, csrc/p2c_encoder.hip) ------------------------------------
+ * (reference modules/movements/transformers.py: six layers, d_model = 2 J, ReLU, dropout 0.1 at four places per layer.)
+ * K20a  multi-head self-attention with dropout on the probabilities, any head width: qkv (S, N, 3, heads, head_dim) = the
+ *   in_proj output viewed, out (S, N, heads head_dim) = concat_h (softmax(scale q k^T) keep / (1 - drop_p)) v. Backward: g_qkv
+ *   from qkv and g_out, the probabilities and the mask recomputed. One launch each, one workgroup per (sequence, head).
+ *   1 <= N <= 64, heads head_dim <= 256 (p2c_attn_drop_supported). Mask element ((s heads + h) N + i) N + j.
+ * K20b  post-norm residual: z = LayerNorm(x + s keep / (1 - drop_p)) over rows of any 2 <= D <= 1024 (gamma / beta (D), biased
+ *   variance, eps inside the root); mean / rstd (rows) written for the backward. Backward: g_x = dz_pre (the residual branch),
+ *   g_s = dz_pre keep / (1 - drop_p), g_gamma / g_beta written (accumulate = 0) or added to; workspace =
+ *   p2c_postnorm_workspace_floats floats; two launches, fixed summation order. Mask element r D + c.
+ * Dropout (drop_state != NULL and drop_p > 0): the hashed stream of p2c_bnorm_desc (forward reads `step`, leaves next = step + 1;
+ * backward reads next - 1, leaves step = next), site drop_site. 0 <= drop_p < 1. With a mask, S heads N^2 >= 2^31 (K20a) and
+ * rows D >= 2^31 (K20b) are refused (P2C_E_SHAPE) before anything is launched. */
+P2C_API int p2c_attn_drop_supported(int32_t N, int32_t heads, int32_t head_dim);
+P2C_API int p2c_attn_drop_fwd(const float *qkv, float *out, float scale, int32_t S, int32_t N, int32_t heads, int32_t head_dim,
+                              void *drop_state, float drop_p, int32_t drop_site, void *stream);
+P2C_API int p2c_attn_drop_bwd(const float *qkv, const float *g_out, float *g_qkv, float scale, int32_t S, int32_t N, int32_t heads,
+                              int32_t head_dim, void *drop_state, float drop_p, int32_t drop_site, void *stream);
+P2C_API int p2c_postnorm_supported(int32_t D);
+P2C_API int64_t p2c_postnorm_workspace_floats(int64_t rows, int32_t D);
+P2C_API int p2c_postnorm_fwd(const float *x, const float *s, const float *gamma, const float *beta, float *z, float *mean,
+                             float *rstd, int64_t rows, int32_t D, float eps, void *drop_state, float drop_p, int32_t drop_site,
+                             void *stream);
+P2C_API int p2c_postnorm_bwd(const float *x, const float *s, const float *gamma, const float *mean, const float *rstd,
+                             const float *g_z, float *g_x, float *g_s, float *g_gamma, float *g_beta, int32_t accumulate,
+                             float *workspace, int64_t rows, int32_t D, void *drop_state, float drop_p, int32_t drop_site,
+                             void *stream);
 
 #ifdef __cplusplus
 }

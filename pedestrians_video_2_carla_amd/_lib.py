@@ -72,7 +72,8 @@ class GemmDesc(ctypes.Structure):
     _fields_ = [('M', ctypes.c_int32), ('N', ctypes.c_int32), ('K', ctypes.c_int32), ('trans_b', ctypes.c_int32),
                 ('a', _f32p), ('lda', ctypes.c_int64), ('b', _f32p), ('ldb', ctypes.c_int64), ('c', _f32p), ('ldc', ctypes.c_int64),
                 ('bias', _f32p), ('act', ctypes.c_int32), ('rows_per_scale', ctypes.c_int32), ('aux', _f32p), ('aux_out', _f32p),
-                ('ldaux', ctypes.c_int64), ('row_scale', _f32p), ('residual', _f32p), ('ldr', ctypes.c_int64)]
+                ('ldaux', ctypes.c_int64), ('row_scale', _f32p), ('residual', _f32p), ('ldr', ctypes.c_int64),
+                ('drop_state', ctypes.c_void_p), ('drop_p', ctypes.c_float), ('drop_site', ctypes.c_int32)]
 
 
 class LstmDesc(ctypes.Structure):
@@ -184,6 +185,15 @@ SYMBOLS = {
     'p2c_attn_small_supported': (ctypes.c_int, [_i32, _i32, _i32]),
     'p2c_attn_small_fwd': (ctypes.c_int, [_vp, _vp, ctypes.c_float, _i32, _i32, _i32, _i32, _vp]),
     'p2c_attn_small_bwd': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _i32, _i32, _i32, _i32, _vp]),
+    'p2c_attn_drop_supported': (ctypes.c_int, [_i32, _i32, _i32]),
+    'p2c_attn_drop_fwd': (ctypes.c_int, [_vp, _vp, ctypes.c_float, _i32, _i32, _i32, _i32, _vp, ctypes.c_float, _i32, _vp]),
+    'p2c_attn_drop_bwd': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _i32, _i32, _i32, _i32, _vp, ctypes.c_float, _i32, _vp]),
+    'p2c_postnorm_supported': (ctypes.c_int, [_i32]),
+    'p2c_postnorm_workspace_floats': (_i64, [_i64, _i32]),
+    'p2c_postnorm_fwd': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, ctypes.c_float, _vp, ctypes.c_float, _i32,
+                                        _vp]),
+    'p2c_postnorm_bwd': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp,
+                                        ctypes.c_float, _i32, _vp]),
     'p2c_atb_group_workspace_floats': (_i64, [ctypes.POINTER(AtbProblem), _i32]),
     'p2c_atb_group': (ctypes.c_int, [ctypes.POINTER(AtbProblem), _i32, _vp, _vp]),
     'p2c_mlp_fwd': (ctypes.c_int, [ctypes.POINTER(MlpDesc), _vp]),

@@ -10,6 +10,9 @@
 //   trans_b = 1 ("NT"): B is (N, K) row-major -- y = x W^T, nn.Linear's forward;
 //   trans_b = 0 ("NN"): B is (K, N) row-major -- dx = dy W, its input gradient.
 //   epilogue, in this order:  v = acc + bias[n];  act 1: (aux_out = v;) v = gelu(v);  act 2: v *= gelu'(aux[m][n]);
+//                             act 3: v = relu(v) keep(m N + n) / (1 - p) (nn.TransformerEncoderLayer's ReLU + dropout; the hashed
+//                             mask of p2c_rec_dev.h, none without drop_state);  act 4: v *= [aux[m][n] > 0] / (1 - p) (its
+//                             backward: aux = act 3's output, positive exactly where the pre-activation was and the mask kept);
 //                             v *= row_scale[m / rows_per_scale];  v += residual[m][n];  C[m][n] = v.
 //
 // Tiling: a workgroup of four wavefronts owns a 128 x BN tile of C (BN = 128: 2 x 2 waves of 64 x 64; BN = 64 / 32: 4 x 1 waves
@@ -23,6 +26,7 @@
 #include <stdlib.h>
 
 #include "../../include/p2c.h"
+#include "p2c_rec_dev.h"
 
 namespace p2c_gemm_impl {
 
@@ -438,6 +442,16 @@ __device__ __forceinline__ void epilogue_rows(const p2c_gemm_desc &d, const f32x
     bias[b] = (d.bias && nok[b]) ? d.bias[n[b]] : 0.f;
   }
   float *const zbase = (ACT == 1) ? d.aux_out : nullptr;
+  p2c_rec::DropRng dr{};
+  if (ACT == 3 && d.drop_state) {       // the launch's keys; the state word the backward reads is left by gemm_kernel's first thread
+    dr.state = static_cast<int32_t *>(d.drop_state);
+    dr.thresh = d.drop_p >= 1.f ? 0xFFFFFFFFu : (uint32_t)((double)d.drop_p * 4294967296.0);
+    dr.scale = d.drop_p >= 1.f ? 0.f : 1.f / (1.f - d.drop_p);
+    dr.site = d.drop_site;
+    p2c_rec::drop_begin(dr, false);
+    p2c_rec::drop_keys_only(dr);
+  }
+  const float relu_scale = (ACT == 4) ? (d.drop_p >= 1.f ? 0.f : 1.f / (1.f - d.drop_p)) : 1.f;
   const bool scale = SCALE == 1 || (SCALE == 2 && d.row_scale != nullptr), res = RES == 1 || (RES == 2 && d.residual != nullptr);
 #pragma unroll
   for (int a = 0; a < TM; ++a)
@@ -447,7 +461,7 @@ __device__ __forceinline__ void epilogue_rows(const p2c_gemm_desc &d, const f32x
       if (!FULL && m >= d.M) continue;
       float *const crow = d.c + (int64_t)m * d.ldc;
       const float *const rrow = res ? d.residual + (int64_t)m * d.ldr : nullptr;
-      const float *const xrow = (ACT == 2) ? d.aux + (int64_t)m * d.ldaux : nullptr;
+      const float *const xrow = (ACT == 2 || ACT == 4) ? d.aux + (int64_t)m * d.ldaux : nullptr;
       float *const zrow = (ACT == 1 && zbase) ? zbase + (int64_t)m * d.ldaux : nullptr;
       const float rs = scale ? d.row_scale[(unsigned)m / (unsigned)d.rows_per_scale] : 1.f;
 #pragma unroll
@@ -459,6 +473,11 @@ __device__ __forceinline__ void epilogue_rows(const p2c_gemm_desc &d, const f32x
           v = gelu(v);
         } else if (ACT == 2) {
           v *= gelu_grad(xrow[n[b]]);
+        } else if (ACT == 3) {
+          v = v > 0.f ? v : 0.f;
+          if (dr.state) v *= p2c_rec::drop_value(dr, (uint32_t)m * (uint32_t)d.N + (uint32_t)n[b]);
+        } else if (ACT == 4) {
+          v *= xrow[n[b]] > 0.f ? relu_scale : 0.f;
         }
         if (scale) v *= rs;
         if (res) v += rrow[n[b]];
@@ -488,6 +507,12 @@ __device__ __forceinline__ void epilogue(const p2c_gemm_desc &d, const f32x16 (&
   } else if (d.act == 2) {
     if (full) epilogue_terms<2, true>(d, acc, mw, nw, li, lk);
     else epilogue_terms<2, false>(d, acc, mw, nw, li, lk);
+  } else if (d.act == 3) {
+    if (full) epilogue_terms<3, true>(d, acc, mw, nw, li, lk);
+    else epilogue_terms<3, false>(d, acc, mw, nw, li, lk);
+  } else if (d.act == 4) {
+    if (full) epilogue_terms<4, true>(d, acc, mw, nw, li, lk);
+    else epilogue_terms<4, false>(d, acc, mw, nw, li, lk);
   } else {
     if (full) epilogue_terms<0, true>(d, acc, mw, nw, li, lk);
     else epilogue_terms<0, false>(d, acc, mw, nw, li, lk);
@@ -515,6 +540,10 @@ __global__ __launch_bounds__(NTH, BN == 128 ? 3 : (BN == 64 ? 5 : 6)) void gemm_
   const int wm = wave % WM, wn = wave / WM;
   const int li = lane & 31, lk = lane >> 5;
   constexpr int ldb_s = TRANS_B ? LDB : BN + 4;
+  if (d.act == 3 && d.drop_state && blockIdx.x == 0 && threadIdx.x == 0) {     // hashed dropout: next = step + 1 (p2c_rec_dev.h)
+    int32_t *st = static_cast<int32_t *>(d.drop_state);
+    st[3] = st[2] + 1;
+  }
 
   f32x16 acc[TM][TN];
 #pragma unroll
@@ -827,11 +856,11 @@ static void launch(const p2c_gemm_desc &d, bool vec, hipStream_t s) {
 #ifdef P2C_GEMM_EXPERIMENTS
   static const int ws_mode = getenv("P2C_GEMM_WS") ? atoi(getenv("P2C_GEMM_WS")) : 0;
   static const int mi16 = getenv("P2C_GEMM_MI16") ? atoi(getenv("P2C_GEMM_MI16")) : 0;
-  if (mi16 && vec && BN == 64) {
+  if (mi16 && vec && BN == 64 && d.act <= 2) {
     hipLaunchKernelGGL((gemm16_kernel<TRANS_B, true>), dim3(grid), dim3(NTH), 0, s, d);
     return;
   }
-  if (ws_mode && vec && d.K >= 256) {           // producer / consumer form: deep products
+  if (ws_mode && vec && d.K >= 256 && d.act <= 2) {           // producer / consumer form: deep products
     hipLaunchKernelGGL((gemm_ws_kernel<BN, TRANS_B, true>), dim3(grid), dim3(2 * NTH), 0, s, d);
     return;
   }
@@ -970,7 +999,9 @@ extern "C" int p2c_gemm(const p2c_gemm_desc *desc, void *stream_) {
   const p2c_gemm_desc d = *desc;
   if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.lda < d.K || d.ldc < d.N) return P2C_E_SHAPE;
   if (d.ldb < (d.trans_b ? d.K : d.N)) return P2C_E_SHAPE;
-  if (d.act < 0 || d.act > 2 || (d.act == 2 && !d.aux) || ((d.aux || d.aux_out) && d.ldaux < d.N)) return P2C_E_ENUM;
+  if (d.act < 0 || d.act > 4 || ((d.act == 2 || d.act == 4) && !d.aux) || ((d.aux || d.aux_out) && d.ldaux < d.N)) return P2C_E_ENUM;
+  if (d.act >= 3 && !(d.drop_p >= 0.f && d.drop_p < 1.f)) return P2C_E_SHAPE;
+  if (d.act == 3 && d.drop_state && (int64_t)d.M * d.N >= (1ll << 31)) return P2C_E_SHAPE;     // 32-bit element index of the mask
   if (d.row_scale && d.rows_per_scale <= 0) return P2C_E_SHAPE;
   if (d.residual && d.ldr < d.N) return P2C_E_SHAPE;
   if ((int64_t)((d.M + BM - 1) / BM) * ((d.N + 31) / 32) > 0x7fffffffll) return P2C_E_SHAPE;

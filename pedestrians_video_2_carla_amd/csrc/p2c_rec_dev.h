@@ -91,6 +91,14 @@ __device__ __forceinline__ void drop_keys(DropRng &r, const bool backward) {
   // it writes, so the moment of the store does not matter.
   if (blockIdx.x == 0 && threadIdx.x == 0) r.state[backward ? 2 : 3] = (int32_t)(step + 1u);
 }
+// The keys of drop_keys without the state write: for a launch whose state word is left by one thread elsewhere (p2c_gemm.hip, where
+// workgroup 0 is not always a tile's).
+__device__ __forceinline__ void drop_keys_only(DropRng &r) {
+  if (!r.state) return;
+  const uint32_t s0 = r.k0, s1 = r.k1, step = r.thresh_step;
+  r.k0 = mix32(s0 ^ (step * 0x9E3779B9u) ^ ((uint32_t)(r.site + 1) * 0x632BE59Bu));
+  r.k1 = mix32(s1 + step + 0x85EBCA6Bu * (uint32_t)(r.site + 1));
+}
 __device__ __forceinline__ float drop_value(const DropRng &r, const uint32_t e) {
   // one Fibonacci multiply spreads the element index, the launch key shifts it, one avalanche finaliser: three 32-bit multiplies
   // on the dependent chain of a time step (two finalisers in a row were four, and ~200 cycles of latency per step)

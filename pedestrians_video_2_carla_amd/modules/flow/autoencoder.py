@@ -12,6 +12,7 @@ from pedestrians_video_2_carla_amd.modules.movements.linear_ae import LinearAE, 
 from pedestrians_video_2_carla_amd.modules.movements.lstm import LSTM
 from pedestrians_video_2_carla_amd.modules.movements.seq2seq import (Seq2Seq, Seq2SeqEmbeddings, Seq2SeqResidualA, Seq2SeqResidualB,
                                                                    Seq2SeqResidualC)
+from pedestrians_video_2_carla_amd.modules.movements.transformers import SimpleTransformer
 from pedestrians_video_2_carla_amd.modules.movements.zero import ZeroMovements
 
 
@@ -19,7 +20,7 @@ class LitAutoencoderFlow(LitBaseFlow):
     @classmethod
     def get_available_models(cls) -> Dict[str, Dict[str, torch.nn.Module]]:
         return {'movements': {m.__name__: m for m in [ZeroMovements, LinearAE, Seq2Seq, Seq2SeqEmbeddings, Seq2SeqResidualA,
-                                                      Seq2SeqResidualB, Seq2SeqResidualC, LSTM]}}
+                                                      Seq2SeqResidualB, Seq2SeqResidualC, LSTM, SimpleTransformer]}}
 
     @classmethod
     def get_default_models(cls) -> Dict[str, torch.nn.Module]:

@@ -1,1 +1,2 @@
 from .lstm import LSTM  # noqa: F401
+from .transformers import SimpleTransformer  # noqa: F401

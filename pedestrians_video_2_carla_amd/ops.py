@@ -1234,10 +1234,12 @@ def atb_group(problems: Sequence[dict]) -> list:
 
 def gemm(a: Tensor, b: Tensor, trans_b: bool, bias: Optional[Tensor] = None, act: int = 0, aux: Optional[Tensor] = None,
          aux_out: Optional[Tensor] = None, row_scale: Optional[Tensor] = None, rows_per_scale: int = 1,
-         residual: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+         residual: Optional[Tensor] = None, out: Optional[Tensor] = None, drop_state: Optional[Tensor] = None,
+         drop_p: float = 0.0, drop_site: int = 0) -> Tensor:
     """K16 (csrc/p2c_gemm.hip): ``out = epilogue(a @ (b.T if trans_b else b))`` on fp32 MFMA, 2-D row-major operands with unit
-    inner stride. Epilogue order: + bias, act (1: GELU, storing the pre-activation in ``aux_out``; 2: times gelu'(``aux``)),
-    times ``row_scale[row // rows_per_scale]``, + ``residual``."""
+    inner stride. Epilogue order: + bias, act (1: GELU, storing the pre-activation in ``aux_out``; 2: times gelu'(``aux``);
+    3: ReLU times the hashed dropout mask of site ``drop_site`` of ``drop_state`` / (1 - ``drop_p``); 4: times
+    [``aux`` > 0] / (1 - ``drop_p``), aux = act 3's output), times ``row_scale[row // rows_per_scale]``, + ``residual``."""
     a, b = _require_device(a, 'a'), _require_device(b, 'b')
     if a.ndim != 2 or b.ndim != 2 or a.stride(1) != 1 or b.stride(1) != 1:
         raise RuntimeError('gemm: 2-D operands with unit inner stride expected')
@@ -1263,6 +1265,7 @@ def gemm(a: Tensor, b: Tensor, trans_b: bool, bias: Optional[Tensor] = None, act
     if residual is not None and (tuple(residual.shape) != (M, N) or residual.stride(1) != 1):
         raise RuntimeError(f'gemm: residual should be ({M}, {N}) with unit inner stride')
     d.residual, d.ldr = _ptr(residual), (residual.stride(0) if residual is not None else 0)
+    d.drop_state, d.drop_p, d.drop_site = _ptr(drop_state), float(drop_p), int(drop_site)
     with torch.cuda.device(a.device):
         _lib.check(_lib.lib().p2c_gemm(ctypes.byref(d), _stream()), 'p2c_gemm')
     return out
@@ -2146,3 +2149,149 @@ class GroupCopy:
                         keep.append(t)
                     s[k] = t.data_ptr()
                 _lib.check(lib.p2c_copy_group(s, d, b, len(ch), stream), 'p2c_copy_group')
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# one post-norm nn.TransformerEncoderLayer as ONE autograd node (K16 + K20 + K12 launches only)
+# ----------------------------------------------------------------------------------------------------------------------
+ENCODER_MAX_TOKENS = 64             # K20a keeps a sequence's N x N probabilities in LDS
+ENCODER_MAX_ELEMENTS = 1 << 31      # the hashed dropout stream indexes elements with 32 bits
+_ENC_WARNED = set()
+
+
+def post_norm_encoder_layer_module_ok(layer) -> bool:
+    """``layer`` is the layer K20 restates: a batch-first, post-norm ``nn.TransformerEncoderLayer`` with ReLU, biases everywhere,
+    one packed in_proj and affine LayerNorms."""
+    if not isinstance(layer, torch.nn.TransformerEncoderLayer):
+        return False
+    sa = layer.self_attn
+    return bool(not layer.norm_first and getattr(layer, 'activation_relu_or_gelu', 0) == 1 and sa.batch_first
+                and sa._qkv_same_embed_dim and sa.in_proj_bias is not None and sa.bias_k is None and not sa.add_zero_attn
+                and sa.out_proj.bias is not None and layer.linear1.bias is not None and layer.linear2.bias is not None
+                and all(n.weight is not None and n.bias is not None for n in (layer.norm1, layer.norm2))
+                and all(t.is_cuda and t.dtype == torch.float32 for t in layer.parameters()))
+
+
+def post_norm_encoder_layer_supported(B: int, T: int, d: int, heads: int, training: bool, dim_ff: int = 2048) -> bool:
+    """The shapes K20 covers: T <= 64 tokens, heads (d / heads) = d <= 256, 2 <= d; with dropout (training) also every mask index
+    below 2^31 -- (B T) x dim_ff for the FFN's. (B T) x dim_ff >= 2^31 in training warns once and returns False: the caller runs the
+    framework layer."""
+    lib = _lib.lib()
+    if not (d % heads == 0 and lib.p2c_attn_drop_supported(int(T), int(heads), int(d // heads)) and lib.p2c_postnorm_supported(int(d))):
+        return False
+    if training and B * T * max(dim_ff, d) >= ENCODER_MAX_ELEMENTS or training and B * heads * T * T >= ENCODER_MAX_ELEMENTS:
+        key = (B, T, d, heads, dim_ff)
+        if key not in _ENC_WARNED:
+            _ENC_WARNED.add(key)
+            warnings.warn(f'post_norm_encoder_layer: {B * T} rows x {dim_ff} has 2^31 elements or more (the dropout masks are indexed '
+                          f'with 32 bits): this layer runs on the framework ops', RuntimeWarning, stacklevel=3)
+        return False
+    return True
+
+
+def _postnorm_fwd(x2d: Tensor, s2d: Tensor, w: Tensor, b: Tensor, eps: float, drop_state, p: float, site: int):
+    rows, D = x2d.shape
+    z = torch.empty_like(x2d)
+    stats = torch.empty(2, rows, dtype=torch.float32, device=x2d.device)
+    _lib.check(_lib.lib().p2c_postnorm_fwd(x2d.data_ptr(), s2d.data_ptr(), w.data_ptr(), b.data_ptr(), z.data_ptr(),
+                                           stats[0].data_ptr(), stats[1].data_ptr(), rows, D, float(eps), _ptr(drop_state),
+                                           float(p), int(site), _stream()), 'p2c_postnorm_fwd')
+    return z, stats
+
+
+def _postnorm_bwd(x2d: Tensor, s2d: Tensor, w: Tensor, b: Tensor, stats: Tensor, gz: Tensor, drop_state, p: float, site: int):
+    """(g_x, g_s, g_gamma, g_beta); the parameter gradients go straight into their sinks when both exist (-> None)."""
+    lib = _lib.lib()
+    rows, D = x2d.shape
+    gx, gs = torch.empty_like(x2d), torch.empty_like(x2d)
+    sw, sb = _sink(w), _sink(b)
+    if sw is None or sb is None:
+        sw = sb = None
+    gw = sw if sw is not None else torch.empty_like(w)
+    gb = sb if sb is not None else torch.empty_like(b)
+    ws = torch.empty(max(1, lib.p2c_postnorm_workspace_floats(rows, D)), dtype=torch.float32, device=x2d.device)
+    _lib.check(lib.p2c_postnorm_bwd(x2d.data_ptr(), s2d.data_ptr(), w.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
+                                    gz.data_ptr(), gx.data_ptr(), gs.data_ptr(), gw.data_ptr(), gb.data_ptr(), int(sw is not None),
+                                    ws.data_ptr(), rows, D, _ptr(drop_state), float(p), int(site), _stream()), 'p2c_postnorm_bwd')
+    return gx, gs, (None if sw is not None else gw), (None if sb is not None else gb)
+
+
+def _wide_weight_grad(gy: Tensor, x: Tensor, w: Tensor, b: Tensor):
+    """``weight_grad`` on the TN GEMM whatever the widths (the FFN's 2048-wide side is past what K12 tiles)."""
+    sw = _sink(w)
+    sb = _sink(b) if sw is not None else None
+    if sb is None:
+        sw = None
+    gw, gb = gemm_tn(gy, x, out=sw, accumulate=sw is not None, bias=True, bias_out=sb)
+    return (None if sw is not None else gw), (None if sb is not None else gb)
+
+
+class PostNormEncoderLayerFunction(torch.autograd.Function):
+    """One post-norm ``nn.TransformerEncoderLayer`` (ReLU, training-mode dropout at four sites) over x (B, T, d) as a single
+    autograd node. Forward, 7 launches: in_proj (K16), attention with dropout on the probabilities (K20a), out_proj (K16),
+    x1 = LayerNorm1(x + drop(sa)) (K20b), h = drop(relu(linear1(x1))) (K16, act 3), linear2 (K16),
+    z = LayerNorm2(x1 + drop(ff)) (K20b). Saved: x, qkv, the attention output, the two pre-residual branch outputs, x1, h and the
+    LayerNorm statistics; no mask (the hashed stream redraws them; h > 0 is the FFN's ReLU gate and mask at once). The
+    parameter gradients go straight into the trainer's sinks inside ``grad_sinks``."""
+
+    @staticmethod
+    def forward(ctx, x, heads, eps1, eps2, probs, drop_state, site, wqkv, bqkv, wo, bo, n1w, n1b, w1, b1, w2, b2, n2w, n2b):
+        x = _require_device(x, 'x').contiguous()
+        B, T, d = x.shape
+        rows, hd = B * T, d // heads
+        p_att, p1, p_ff, p2 = probs
+        st = lambda p: drop_state if (drop_state is not None and p > 0) else None      # noqa: E731
+        x2 = x.view(rows, d)
+        scale = 1.0 / float(hd) ** 0.5
+        with torch.cuda.device(x.device):
+            qkv = gemm(x2, wqkv, True, bias=bqkv)
+            att = torch.empty(rows, d, dtype=torch.float32, device=x.device)
+            _lib.check(_lib.lib().p2c_attn_drop_fwd(qkv.data_ptr(), att.data_ptr(), scale, B, T, heads, hd, _ptr(st(p_att)),
+                                                    float(p_att), int(site), _stream()), 'p2c_attn_drop_fwd')
+            s1 = gemm(att, wo, True, bias=bo)
+            x1, st1 = _postnorm_fwd(x2, s1, n1w, n1b, eps1, st(p1), p1, site + 1)
+            h = gemm(x1, w1, True, bias=b1, act=3, drop_state=st(p_ff), drop_p=p_ff, drop_site=site + 2)
+            s2 = gemm(h, w2, True, bias=b2)
+            out, st2 = _postnorm_fwd(x1, s2, n2w, n2b, eps2, st(p2), p2, site + 3)
+        ctx.save_for_backward(x2, qkv, att, s1, x1, st1, h, s2, st2)
+        ctx.params = (wqkv, bqkv, wo, bo, n1w, n1b, w1, b1, w2, b2, n2w, n2b)
+        ctx.cfg = (B, T, d, heads, scale, probs, drop_state, site)
+        return out.view(B, T, d)
+
+    @staticmethod
+    def backward(ctx, g):
+        x2, qkv, att, s1, x1, st1, h, s2, st2 = ctx.saved_tensors
+        wqkv, bqkv, wo, bo, n1w, n1b, w1, b1, w2, b2, n2w, n2b = ctx.params
+        B, T, d, heads, scale, (p_att, p1, p_ff, p2), drop_state, site = ctx.cfg
+        st = lambda p: drop_state if (drop_state is not None and p > 0) else None      # noqa: E731
+        g = _require_device(g, 'grad').contiguous().view(B * T, d)
+        with torch.cuda.device(g.device):
+            gx1, gs2, gn2w, gn2b = _postnorm_bwd(x1, s2, n2w, n2b, st2, g, st(p2), p2, site + 3)
+            dpre = gemm(gs2, w2, False, act=4, aux=h, drop_p=p_ff)                     # relu' and the FFN mask from h > 0
+            gw2, gb2 = _wide_weight_grad(gs2, h, w2, b2)
+            gw1, gb1 = _wide_weight_grad(dpre, x1, w1, b1)
+            gx1 = gemm(dpre, w1, False, residual=gx1)                                 # + the gradient over the second residual
+            gx, gs1, gn1w, gn1b = _postnorm_bwd(x2, s1, n1w, n1b, st1, gx1, st(p1), p1, site + 1)
+            gatt = gemm(gs1, wo, False)
+            gwo, gbo = weight_grad(gs1, att, wo, bo)
+            gqkv = torch.empty_like(qkv)
+            _lib.check(_lib.lib().p2c_attn_drop_bwd(qkv.data_ptr(), gatt.data_ptr(), gqkv.data_ptr(), scale, B, T, heads, d // heads,
+                                                    _ptr(st(p_att)), float(p_att), int(site), _stream()), 'p2c_attn_drop_bwd')
+            gwq, gbq = weight_grad(gqkv, x2, wqkv, bqkv)
+            gx = gemm(gqkv, wqkv, False, residual=gx).view(B, T, d) if ctx.needs_input_grad[0] else None
+        return (gx, None, None, None, None, None, None, gwq, gbq, gwo, gbo, gn1w, gn1b, gw1, gb1, gw2, gb2, gn2w, gn2b)
+
+
+def post_norm_encoder_layer(x: Tensor, layer, heads: int, drop_state: Optional[Tensor], site: int) -> Tensor:
+    """``layer(x)`` for a post-norm ``nn.TransformerEncoderLayer`` (``post_norm_encoder_layer_module_ok``) over x (B, T, d) on
+    the device: ``PostNormEncoderLayerFunction``. In training the four dropout masks come from ``drop_state`` (sites ``site`` ...
+    ``site + 3``: attention probabilities, after out_proj, after the ReLU, after linear2); ``drop_state=None`` draws none."""
+    sa = layer.self_attn
+    training = layer.training
+    probs = tuple(float(p) if training else 0.0 for p in (sa.dropout, layer.dropout1.p, layer.dropout.p, layer.dropout2.p))
+    if any(p > 0 for p in probs) and drop_state is None:
+        raise RuntimeError('post_norm_encoder_layer: dropout is live but no drop_state was given')
+    return PostNormEncoderLayerFunction.apply(
+        x, int(heads), float(layer.norm1.eps), float(layer.norm2.eps), probs, drop_state, int(site), sa.in_proj_weight,
+        sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias, layer.norm1.weight, layer.norm1.bias, layer.linear1.weight,
+        layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, layer.norm2.weight, layer.norm2.bias)

@@ -20,7 +20,12 @@ import torch.distributed as dist
 
 class FlatParameters:
     def __init__(self, params: Iterable[torch.nn.Parameter]):
-        self.params: List[torch.nn.Parameter] = [p for p in params if p.requires_grad]
+        params = [p for p in params if p.requires_grad]
+        # a parameter marked ``p2c_unused`` never takes part in forward (SimpleTransformer's ``encoder_layer`` template): its
+        # gradient stays None, so the reference's optimizer never updates it -- weight decay included. It stays out of the flat
+        # buffers, where a zero gradient would still let decoupled weight decay shrink it.
+        self.unused: List[torch.nn.Parameter] = [p for p in params if getattr(p, 'p2c_unused', False)]
+        self.params: List[torch.nn.Parameter] = [p for p in params if not getattr(p, 'p2c_unused', False)]
         if not self.params:
             raise ValueError('no trainable parameters')
         dev, dt = self.params[0].device, self.params[0].dtype
@@ -81,6 +86,8 @@ class GradientExchange:
     def broadcast_parameters(self, src: int = 0):
         if self.enabled:
             dist.broadcast(self.flat.flat_param.data, src=src, group=self.group)
+            for p in self.flat.unused:               # (DDP broadcasts every parameter at wrap time, used or not)
+                dist.broadcast(p.data, src=src, group=self.group)
 
     def broadcast_buffers(self, module: torch.nn.Module, src: int = 0):
         """Module buffers (BatchNorm running statistics of LinearAEResidual ...) from rank ``src``: what Lightning's DDP
