@@ -591,7 +591,8 @@ typedef struct p2c_gemm_desc {
   const float *residual; int64_t ldr;
   /* act 3 / 4 (nn.TransformerEncoderLayer's FFN): act 3: v = relu(v) keep(m N + n) / (1 - drop_p) with the hashed mask of site
    * drop_site of drop_state (the 4-word stream of p2c_bnorm_desc: reads `step`, leaves next = step + 1; drop_state NULL: relu
-   * alone); act 4: v *= [aux[m][n] > 0] / (1 - drop_p), aux = act 3's output -- relu' and the kept mask in one test, so the
+   * alone, which needs drop_p == 0 -- act 4 scales by 1 / (1 - drop_p) with or without a state, so act 3 refuses drop_p > 0
+   * without one, P2C_E_SHAPE); act 4: v *= [aux[m][n] > 0] / (1 - drop_p), aux = act 3's output -- relu' and the kept mask in one test, so the
    * backward needs neither the pre-activation nor a mask tensor. 0 <= drop_p < 1; act 3 with drop_state refuses M N >= 2^31
    * (P2C_E_SHAPE, nothing launched). Zero for acts 0..2. */
   void *drop_state;

@@ -1002,6 +1002,7 @@ extern "C" int p2c_gemm(const p2c_gemm_desc *desc, void *stream_) {
   if (d.act < 0 || d.act > 4 || ((d.act == 2 || d.act == 4) && !d.aux) || ((d.aux || d.aux_out) && d.ldaux < d.N)) return P2C_E_ENUM;
   if (d.act >= 3 && !(d.drop_p >= 0.f && d.drop_p < 1.f)) return P2C_E_SHAPE;
   if (d.act == 3 && d.drop_state && (int64_t)d.M * d.N >= (1ll << 31)) return P2C_E_SHAPE;     // 32-bit element index of the mask
+  if (d.act == 3 && !d.drop_state && d.drop_p > 0.f) return P2C_E_SHAPE;    // relu without the 1 / (1 - p) of act 4: no pair
   if (d.row_scale && d.rows_per_scale <= 0) return P2C_E_SHAPE;
   if (d.residual && d.ldr < d.N) return P2C_E_SHAPE;
   if ((int64_t)((d.M + BM - 1) / BM) * ((d.N + 31) / 32) > 0x7fffffffll) return P2C_E_SHAPE;

@@ -1232,6 +1232,15 @@ def atb_group(problems: Sequence[dict]) -> list:
     return results
 
 
+def _check_out(t: Tensor, shape: tuple, device, what: str) -> None:
+    """An output the kernel writes in place: the given shape, float32 on the operands' device, unit inner stride (a 1-D output
+    dense) -- anything else would be written past or beside the tensor."""
+    if (tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != device or t.stride(-1) != 1
+            or (t.ndim == 2 and t.stride(0) < shape[1])):
+        raise RuntimeError(f'{what} should be a float32 {shape} tensor on {device} with unit inner stride, got {tuple(t.shape)} '
+                           f'{t.dtype} on {t.device} with strides {t.stride()}')
+
+
 def gemm(a: Tensor, b: Tensor, trans_b: bool, bias: Optional[Tensor] = None, act: int = 0, aux: Optional[Tensor] = None,
          aux_out: Optional[Tensor] = None, row_scale: Optional[Tensor] = None, rows_per_scale: int = 1,
          residual: Optional[Tensor] = None, out: Optional[Tensor] = None, drop_state: Optional[Tensor] = None,
@@ -1249,10 +1258,15 @@ def gemm(a: Tensor, b: Tensor, trans_b: bool, bias: Optional[Tensor] = None, act
         raise RuntimeError(f'gemm: inner dimensions differ: {tuple(a.shape)} x {tuple(b.shape)} (trans_b={trans_b})')
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=a.device)
+    _check_out(out, (M, N), a.device, 'gemm: out')
+    if bias is not None:
+        bias = _require_device(bias, 'bias')
+        if tuple(bias.shape) != (N,):
+            raise RuntimeError(f'gemm: bias should hold {N} floats, got {tuple(bias.shape)}')
     d = _lib.GemmDesc()
     d.M, d.N, d.K, d.trans_b = M, N, K, int(bool(trans_b))
     d.a, d.lda, d.b, d.ldb, d.c, d.ldc = a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), out.data_ptr(), out.stride(0)
-    d.bias = _ptr(None if bias is None else _require_device(bias, 'bias'))
+    d.bias = _ptr(bias)
     d.act, d.rows_per_scale = int(act), int(rows_per_scale)
     for t, name in ((aux, 'aux'), (aux_out, 'aux_out')):
         if t is not None and (tuple(t.shape) != (M, N) or t.stride(1) != 1):
@@ -1283,9 +1297,12 @@ def gemm_tn(a: Tensor, b: Tensor, out: Optional[Tensor] = None, accumulate: bool
     K, M, N = a.shape[0], a.shape[1], b.shape[1]
     if out is None:
         out, accumulate = torch.empty(M, N, dtype=torch.float32, device=a.device), False
+    _check_out(out, (M, N), a.device, 'gemm_tn: out')
     flags = (1 if accumulate else 0) | (2 if (bias and bias_out is not None and accumulate) else 0)
     if bias and bias_out is None:
         bias_out = torch.empty(M, dtype=torch.float32, device=a.device)
+    if bias:
+        _check_out(bias_out, (M,), a.device, 'gemm_tn: bias_out')
     lib = _lib.lib()
     ws = torch.empty(max(1, lib.p2c_gemm_tn_workspace_floats(M, N, K)), dtype=torch.float32, device=a.device)
     with torch.cuda.device(a.device):

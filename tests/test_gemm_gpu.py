@@ -7,6 +7,7 @@ import math
 
 import pytest
 import torch
+from test_gemm_forms_gpu import c_gemm, c_gemm_tn, fwd_form, tn_form
 
 pytestmark = pytest.mark.gpu
 
@@ -45,7 +46,8 @@ def test_gemm_plain_matches_fp64(M, N, K, trans_b):
                                    (2050, 257, 129), (4096, 132, 100), (640, 36, 260)])    # (the last two: buffer-load forms, ragged tiles)
 def test_gemm_tn_matches_fp64_is_reproducible_and_accumulates(K, M, N):
     """dW = dy^T x for wide layers: split-K slabs added in a fixed order -- same bits on every call; accumulate adds to the sink;
-    strided operands (column slices) take the dword loads."""
+    operands that are column slices of wider tensors, passed as they are through the C ABI (lda = M + 3, ldb = N + 5, bases 4 /
+    8 bytes off alignment) take the dword loads, and an output with ldc > N the scalar finish kernel."""
     from pedestrians_video_2_carla_amd import ops
     torch.manual_seed(K + M)
     a, b = torch.randn(K, M, device=dev()), torch.randn(K, N, device=dev())
@@ -58,8 +60,11 @@ def test_gemm_tn_matches_fp64_is_reproducible_and_accumulates(K, M, N):
     ops.gemm_tn(a, b, out=sink, accumulate=True)
     assert rel(sink, before.double() + want) < 2e-6 * math.sqrt(K) + 1e-7
     wide_a, wide_b = torch.randn(K, M + 3, device=dev()), torch.randn(K, N + 5, device=dev())
-    c2 = ops.gemm_tn(wide_a[:, 1:M + 1], wide_b[:, 2:N + 2])
-    assert rel(c2, wide_a[:, 1:M + 1].double().t() @ wide_b[:, 2:N + 2].double()) < 2e-6 * math.sqrt(K) + 1e-7
+    sa, sb = wide_a[:, 1:M + 1], wide_b[:, 2:N + 2]
+    assert tn_form(M, N, K, sa.data_ptr(), sa.stride(0), sb.data_ptr(), sb.stride(0)) == 'dword'
+    c2 = torch.zeros(M, N + 1, device=dev())[:, :N]
+    assert c_gemm_tn(sa, sb, c2) == 0
+    assert rel(c2, sa.double().t() @ sb.double()) < 2e-6 * math.sqrt(K) + 1e-7
 
 
 @pytest.mark.parametrize('K,M,N,per', [(9 * 500, 832, 256, 9), (26 * 300, 140, 200, 26), (26 * 300, 32, 96, 26), (64, 5, 3, 1),
@@ -87,8 +92,9 @@ def test_weight_gradient_with_row_factor_and_bias_in_one_pass(K, M, N, per):
 
 def test_gemm_epilogue_and_strided_operands():
     """bias, GELU with the stored pre-activation, gelu' of a stored tensor, per-sample factor, residual (also aliased with the
-    output), operands that are column slices of wider tensors (leading dimension > width; not 16-byte aligned -> dword loads)."""
-    from pedestrians_video_2_carla_amd import ops
+    output), operands that are column slices of wider tensors passed as they are through the C ABI: forward A with lda = K + 5
+    and a base 4 bytes off alignment (dword loads), W with ldb = K + 4; backward gy with lda = N + 8 and W with ldb = K + 4,
+    both 16-byte aligned (16-byte loads with leading dimensions > width)."""
     d = dev()
     torch.manual_seed(3)
     M, N, K, rows_per = 9 * 211, 200, 72, 9
@@ -97,7 +103,9 @@ def test_gemm_epilogue_and_strided_operands():
     bias, res = torch.randn(N, device=d), torch.randn(M, N, device=d)
     scale = (torch.rand(M // rows_per, device=d) > 0.3).float() / 0.7
     z = torch.empty(M, N, device=d)
-    y = ops.gemm(A, W, True, bias=bias, act=1, aux_out=z, row_scale=scale, rows_per_scale=rows_per, residual=res)
+    y = torch.empty(M, N, device=d)
+    assert fwd_form(M, N, K, True, A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0)) == 'dword'
+    assert c_gemm(A, W, True, y, bias=bias, act=1, aux_out=z, row_scale=scale, rows_per_scale=rows_per, residual=res) == 0
     z64 = A.double() @ W.double().t() + bias.double()
     want = gelu64(z64) * scale.double().repeat_interleave(rows_per).view(-1, 1) + res.double()
     assert rel(z, z64) < 2e-5 and rel(y, want) < 2e-5
@@ -106,7 +114,8 @@ def test_gemm_epilogue_and_strided_operands():
     dz_res = torch.randn(M, K, device=d)
     zz = torch.randn(M, K, device=d)
     out = dz_res.clone()
-    ops.gemm(gy, W.contiguous(), False, act=2, aux=zz, row_scale=scale, rows_per_scale=rows_per, residual=out, out=out)
+    assert fwd_form(M, K, N, False, gy.data_ptr(), gy.stride(0), W.data_ptr(), W.stride(0)) == 'VEC'
+    assert c_gemm(gy, W, False, out, act=2, aux=zz, row_scale=scale, rows_per_scale=rows_per, residual=out) == 0
     z6 = zz.double()
     gelu_grad = 0.5 * (1 + torch.erf(z6 / math.sqrt(2.0))) + z6 * torch.exp(-0.5 * z6 * z6) / math.sqrt(2 * math.pi)
     want = (gy.double() @ W.double()) * gelu_grad * scale.double().repeat_interleave(rows_per).view(-1, 1) + dz_res.double()
