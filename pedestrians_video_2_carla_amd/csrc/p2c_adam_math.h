@@ -1,5 +1,6 @@
 // p2c_adam_math.h -- the AdamW / Adam update formula shared by the stand-alone optimizer kernel (p2c_optim.hip) and the
-// fused "reduce + update" tail of the MLP backward (p2c_mlp.hip): one definition, bit-identical results.
+// fused "reduce + update" tails of the MLP backward (p2c_mlp.hip) and of the two-launch train step (p2c_train.hip): one
+// definition, bit-identical results.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,8 +35,10 @@ __device__ __forceinline__ Coefs coefs(const p2c_adamw_desc &d, float step) {
   return c;
 }
 
-// No FMA contraction in here: the formula is inlined into three kernels (adamw_kernel, the MLP's gradient reductions, the
-// two-launch train step) and must round the same way in each, whatever the surrounding code lets the compiler fuse.
+// No FMA contraction in here: the formula is inlined into five kernels -- adamw_kernel (p2c_optim.hip), mlp_reduce_kernel and
+// mlp_reduce_small_kernel (p2c_mlp.hip: fused / split weight gradient), train_wgrad_kernel and wgrad_reduce_kernel
+// (p2c_train.hip: two-launch train step below / from wgrad_stream_min_b clips) -- and must round the same way in each,
+// whatever the surrounding code lets the compiler fuse (tests/test_adam_sites_gpu.py compares them bit for bit).
 template <bool ADAMW>
 __device__ __forceinline__ void update(const Coefs &c, float &p, float g, float &m, float &v) {
 #pragma clang fp contract(off)

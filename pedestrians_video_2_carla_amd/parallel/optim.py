@@ -41,6 +41,28 @@ class FlatAdamW(torch.optim.Optimizer):
                          'exp_avg': torch.zeros_like(p, memory_format=torch.preserve_format),
                          'exp_avg_sq': torch.zeros_like(p, memory_format=torch.preserve_format)}
 
+    def load_state_dict(self, state_dict):
+        """torch leaves ``state['step']`` where the loaded dict had it (a host tensor for a checkpoint read with
+        ``map_location='cpu'`` or for the state of a plain torch.optim.AdamW): the kernels read the counter through a device
+        pointer, so all three state tensors are brought to the parameter's device here, the counter as a 0-dim fp32 tensor."""
+        super().load_state_dict(state_dict)
+        (p,) = self.param_groups[0]['params']
+        st = self.state[p]
+        step = st.get('step', 0.0)
+        if isinstance(step, torch.Tensor):
+            step = step.detach().to(device=p.device, dtype=torch.float32).reshape(()).clone()
+        else:
+            step = torch.tensor(float(step), dtype=torch.float32, device=p.device)
+        st['step'] = step
+        for k in ('exp_avg', 'exp_avg_sq'):
+            t = st.get(k)
+            if not isinstance(t, torch.Tensor) or t.shape != p.shape:
+                if t is not None:
+                    raise ValueError(f'FlatAdamW.load_state_dict: {k} does not have the flat parameter\'s shape')
+                t = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st[k] = t.detach().to(device=p.device, dtype=torch.float32).contiguous()
+        self._uploaded = None                     # the loaded param_groups are uploaded by the next sync_hyper()
+
     def set_scatter(self, index: torch.Tensor, dst: torch.Tensor):
         """After every step, parameter i is also written to ``dst[index[i]]`` (index < 0: not copied)."""
         (p,) = self.param_groups[0]['params']
