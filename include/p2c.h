@@ -416,7 +416,8 @@ P2C_API int p2c_decoder_bwd(const p2c_decoder_desc *desc, void *stream);
  * p2c_eval_pck: PCK (metrics/pck.py:66-98): state[0] += correct, state[2] += total. pred (N,Jp,Cp), gt (N,Jg,Cg), N = B*T,
  * Jg <= 64; pmap[Jg] = prediction joint paired with gt joint i or -1; mask_src = targets['projection_2d'] (N,Jg,Cg) or NULL
  * (= gt); hips_joint = gt joint that is never masked or -1; norm_mode 0 = bounding-box diagonal, 1 = |neck - hips| of the
- * gt frame. partials: p2c_eval_workspace_floats(N) floats. */
+ * gt frame; in norm_mode 1 hips_idx[n_hips] / neck_idx[n_neck] (one or two gt joints each, averaged) must lie in [0, Jg):
+ * anything else is refused with P2C_E_INDEX, as the normaliser refuses it. partials: p2c_eval_workspace_floats(N) floats. */
 P2C_API int64_t p2c_eval_workspace_floats(int64_t units);
 P2C_API int p2c_eval_pose3d(const float *pred, const float *gt, int32_t B, int32_t T, int32_t Jg, const int32_t *gmap,
                     const int32_t *pred_hips, int32_t n_pred_hips, const int32_t *gt_hips, int32_t n_gt_hips,

@@ -219,8 +219,14 @@ extern "C" int p2c_eval_pck(const float *pred, const float *gt, const float *mas
   a.mask_missing = mask_missing ? 1 : 0, a.hips_joint = hips_joint, a.norm_mode = norm_mode;
   if (norm_mode == 1) {
     if (!hips_idx || !neck_idx || n_hips < 1 || n_hips > 2 || n_neck < 1 || n_neck > 2) return P2C_E_INDEX;
-    for (int i = 0; i < n_hips; ++i) a.hips_idx[i] = hips_idx[i];
-    for (int i = 0; i < n_neck; ++i) a.neck_idx[i] = neck_idx[i];
+    for (int i = 0; i < n_hips; ++i) {                           // lanes of the frame's own group only (as norm_launch, p2c_aux.hip)
+      if (hips_idx[i] < 0 || hips_idx[i] >= Jg) return P2C_E_INDEX;
+      a.hips_idx[i] = hips_idx[i];
+    }
+    for (int i = 0; i < n_neck; ++i) {
+      if (neck_idx[i] < 0 || neck_idx[i] >= Jg) return P2C_E_INDEX;
+      a.neck_idx[i] = neck_idx[i];
+    }
     a.n_hips = n_hips, a.n_neck = n_neck;
   }
   a.threshold = threshold, a.near_zero = near_zero;
