@@ -537,8 +537,10 @@ P2C_API int p2c_graph_node_counts(void *graph, int32_t *n_total, int32_t *n_kern
  * 104 in the temporal ones). qkv (S, N, 3, heads, head_dim) = the qkv projection's output viewed; out (S, N, heads*head_dim)
  * = softmax(scale * q k^T) v per head, heads concatenated. Backward: from qkv and g_out (S, N, heads*head_dim) to g_qkv (the
  * layout of qkv); the probabilities are recomputed. One launch each; one workgroup per sequence with everything in LDS:
- * N <= 64, heads*head_dim % 4 == 0 and (4 N heads head_dim + 2 heads N^2) floats <= 156 KB (p2c_attn_small_supported). No
- * attention dropout, no mask. */
+ * N <= 64, heads*head_dim % 4 == 0 and (N (4 heads head_dim + 8) + 2 heads N^2) floats <= 156 KB -- the backward's image: q, k,
+ * v and g_out rows with 4 floats of padding each, scores and their gradients (p2c_attn_small_supported). qkv, out, g_out and
+ * g_qkv are read and written 16 bytes at a time: a pointer that is not 16-byte aligned is refused (P2C_E_SHAPE), as K15 does.
+ * No attention dropout, no mask. */
 P2C_API int p2c_attn_small_supported(int32_t N, int32_t heads, int32_t head_dim);
 P2C_API int p2c_attn_small_fwd(const float *qkv, float *out, float scale, int32_t S, int32_t N, int32_t heads, int32_t head_dim,
                        void *stream);
@@ -653,7 +655,8 @@ P2C_API int p2c_bnorm_bwd(const p2c_bnorm_desc *desc, float *workspace, void *st
  *   from qkv and g_out, the probabilities and the mask recomputed. One launch each, one workgroup per (sequence, head).
  *   1 <= N <= 64, heads head_dim <= 256 (p2c_attn_drop_supported). Mask element ((s heads + h) N + i) N + j.
  * K20b  post-norm residual: z = LayerNorm(x + s keep / (1 - drop_p)) over rows of any 2 <= D <= 1024 (gamma / beta (D), biased
- *   variance, eps inside the root); mean / rstd (rows) written for the backward. Backward: g_x = dz_pre (the residual branch),
+ *   variance, eps inside the root); mean / rstd (rows) written (the backward reads rstd and forms the row mean again, in fp64
+ *   as the forward does: u - mean survives rows whose elements nearly coincide). Backward: g_x = dz_pre (the residual branch),
  *   g_s = dz_pre keep / (1 - drop_p), g_gamma / g_beta written (accumulate = 0) or added to; workspace =
  *   p2c_postnorm_workspace_floats floats; two launches, fixed summation order. Mask element r D + c.
  * Dropout (drop_state != NULL and drop_p > 0): the hashed stream of p2c_bnorm_desc (forward reads `step`, leaves next = step + 1;

@@ -12,7 +12,11 @@
 //                 q, k, v, g_out are read from global memory (a head's rows are a few KB: L1 / L2 hits after the first touch).
 //       Mask element e = ((s heads + h) N + i) N + j of the (S, heads, N, N) probabilities.
 // K20b  post-norm residual: z = LayerNorm(x + s keep / (1 - p)), s = the out_proj / linear2 output, any 2 <= D <= 1024.
-//       forward : mean, rstd (rows) are saved; the sum u = x + s keep / (1 - p) is not: the backward forms it again (same fmaf).
+//       forward : mean, rstd (rows) are saved; the sum u = x + s keep / (1 - p) is not: the backward forms it again (same fma).
+//                 u, the row mean and u - mean are formed in fp64 (forward and backward alike, the backward summing the row
+//                 again: the saved fp32 mean serves callers only): a row whose elements lie within 1e-3 of each other -- any
+//                 row at D = 2 with x1 + s1 ~ x2 + s2 -- loses u - mean to the rounding of u and of the mean in fp32 (seen:
+//                 dx 3e-4 of the cancellation scale off, z 2e-5). The squares, rstd and everything behind them stay fp32.
 //       backward: dz_pre = rstd (gg - mean(gg) - xh mean(gg xh)), gg = dz gamma, xh = (u - mean) rstd;
 //                 dx = dz_pre (the residual branch), ds = dz_pre keep / (1 - p); d gamma = sum_rows dz xh, d beta = sum_rows dz in
 //                 per-workgroup partials added in a fixed order by a second launch (K15's scheme: bitwise reproducible).
@@ -167,6 +171,12 @@ __device__ __forceinline__ float group_sum(float v) {
   for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+template <int G>
+__device__ __forceinline__ double group_sum_f64(double v) {
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 __device__ __forceinline__ float keep_of(const DropRng &d, int64_t r, int D, int col) {
   return d.state ? p2c_rec::drop_value(d, (uint32_t)(r * D + col)) : 1.f;
 }
@@ -186,33 +196,33 @@ __global__ __launch_bounds__(THREADS) void postnorm_fwd_kernel(NormArgs a) {
     gm[k] = col < D ? a.gamma[col] : 0.f, bt[k] = col < D ? a.beta[col] : 0.f;
   }
   const float inv_d = 1.f / (float)D;
+  const double inv_d64 = 1.0 / (double)D;
   for (int64_t r0 = (int64_t)blockIdx.x * RPB; r0 < a.rows; r0 += (int64_t)gridDim.x * RPB) {
     const int64_t r = r0 + slot;
     const bool live = r < a.rows;
-    float u[KV], s1 = 0.f;
+    double u[KV], s1 = 0.0;
 #pragma unroll
     for (int k = 0; k < KV; ++k) {
       const int col = k * G + l;
-      u[k] = 0.f;
-      if (live && col < D) u[k] = fmaf(a.s[r * D + col], keep_of(a.drop, r, D, col), a.x[r * D + col]);
+      u[k] = 0.0;
+      if (live && col < D) u[k] = fma((double)a.s[r * D + col], (double)keep_of(a.drop, r, D, col), (double)a.x[r * D + col]);
       s1 += u[k];
     }
-    const float mean = group_sum<G>(s1) * inv_d;
-    float q = 0.f;
+    const double mean = group_sum_f64<G>(s1) * inv_d64;
+    float t[KV], q = 0.f;
 #pragma unroll
-    for (int k = 0; k < KV; ++k)
-      if (k * G + l < D) {
-        const float t = u[k] - mean;
-        q = fmaf(t, t, q);
-      }
+    for (int k = 0; k < KV; ++k) {
+      t[k] = (k * G + l < D) ? (float)(u[k] - mean) : 0.f;
+      q = fmaf(t[k], t[k], q);
+    }
     const float rstd = rsqrtf(group_sum<G>(q) * inv_d + a.eps);
     if (!live) continue;
 #pragma unroll
     for (int k = 0; k < KV; ++k) {
       const int col = k * G + l;
-      if (col < D) a.z[r * D + col] = fmaf((u[k] - mean) * rstd, gm[k], bt[k]);
+      if (col < D) a.z[r * D + col] = fmaf(t[k] * rstd, gm[k], bt[k]);
     }
-    if (l == 0) a.mean[r] = mean, a.rstd[r] = rstd;
+    if (l == 0) a.mean[r] = (float)mean, a.rstd[r] = rstd;
   }
 }
 
@@ -232,19 +242,28 @@ __global__ __launch_bounds__(THREADS) void postnorm_bwd_kernel(NormArgs a) {
     dg[k] = db[k] = 0.f;
   }
   const float inv_d = 1.f / (float)D;
+  const double inv_d64 = 1.0 / (double)D;
   for (int64_t r0 = (int64_t)blockIdx.x * RPB; r0 < a.rows; r0 += (int64_t)gridDim.x * RPB) {
     const int64_t r = r0 + slot;
     const bool live = r < a.rows;
-    const float mean = live ? a.mean[r] : 0.f, rstd = live ? a.rstd[r] : 0.f;
+    const float rstd = live ? a.rstd[r] : 0.f;
     float xh[KV], gg[KV], keep[KV], s1 = 0.f, s2 = 0.f;
+    double u[KV], s0 = 0.0;
 #pragma unroll
     for (int k = 0; k < KV; ++k) {
       const int col = k * G + l;
       const bool ok = live && col < D;
       keep[k] = ok ? keep_of(a.drop, r, D, col) : 0.f;
-      const float u = ok ? fmaf(a.s[r * D + col], keep[k], a.x[r * D + col]) : 0.f;
+      u[k] = ok ? fma((double)a.s[r * D + col], (double)keep[k], (double)a.x[r * D + col]) : 0.0;
+      s0 += u[k];
+    }
+    const double mean = group_sum_f64<G>(s0) * inv_d64;       // (the forward's operations: the same bits)
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+      const int col = k * G + l;
+      const bool ok = live && col < D;
       const float g = ok ? a.gz[r * D + col] : 0.f;
-      xh[k] = ok ? (u - mean) * rstd : 0.f;
+      xh[k] = ok ? (float)(u[k] - mean) * rstd : 0.f;
       gg[k] = g * gm[k];
       s1 += gg[k];
       s2 = fmaf(gg[k], xh[k], s2);

@@ -1743,6 +1743,12 @@ def small_attention_supported(N: int, heads: int, head_dim: int) -> bool:
     return bool(_lib.lib().p2c_attn_small_supported(int(N), int(heads), int(head_dim)))
 
 
+def _aligned16(t: Tensor) -> Tensor:
+    """K14 moves 16 bytes at a time and refuses other pointers: a dense view that starts inside a larger buffer (``buf[1:]``
+    passes ``contiguous()`` unchanged) is copied into an allocation of its own."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 class SmallAttentionFunction(torch.autograd.Function):
     """out (S,N,heads*head_dim) = concat_h softmax(scale q_h k_h^T) v_h from qkv (S,N,3,heads,head_dim): one launch forward, one
     backward (probabilities recomputed), one workgroup per sequence."""
@@ -1750,7 +1756,7 @@ class SmallAttentionFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, scale: float):
         lib = _lib.lib()
-        qkv = _require_device(qkv, 'qkv')
+        qkv = _aligned16(_require_device(qkv, 'qkv'))
         S, N, three, Hh, D = qkv.shape
         if three != 3 or not small_attention_supported(N, Hh, D):
             raise RuntimeError(f'small attention: unsupported shape {tuple(qkv.shape)}')
@@ -1766,7 +1772,7 @@ class SmallAttentionFunction(torch.autograd.Function):
         lib = _lib.lib()
         (qkv,) = ctx.saved_tensors
         S, N, _, Hh, D = qkv.shape
-        g_out = _require_device(g_out, 'grad out')
+        g_out = _aligned16(_require_device(g_out, 'grad out'))
         g_qkv = torch.empty_like(qkv)
         with torch.cuda.device(qkv.device):
             _lib.check(lib.p2c_attn_small_bwd(qkv.data_ptr(), g_out.data_ptr(), g_qkv.data_ptr(), ctx.scale, S, N, Hh, D, _stream()),
