@@ -677,6 +677,37 @@ P2C_API int p2c_postnorm_bwd(const float *x, const float *s, const float *gamma,
                              float *workspace, int64_t rows, int32_t D, void *drop_state, float drop_p, int32_t drop_site,
                              void *stream);
 
+/* ---- fused ReLU stack (K21, csrc/p2c_relu_stack.hip) ---------------------------------------------------------------------------
+ * The front end of Seq2SeqFlatEmbeddings (reference modules/movements/seq2seq/seq2seq_flat_embeddings.py:39-44, 62-73):
+ * h_0 = x, h_{l+1} = relu(W_l h_l + b_l) for l = 0 .. n_layers - 1 (the ReLU after the last layer included) over the N = B T rows
+ * of x (B T, dims[0]); W_l row-major (dims[l+1], dims[l]) as nn.Linear.weight, b_l (dims[l+1]).
+ * Forward (one launch): y is written SEQUENCE-FIRST, (T, B, dims[n_layers]): input row b T + t goes to output row t' B + b with
+ *   t' = T - 1 - t when flip != 0 (invert_sequence), else t' = t.
+ * Backward (two launches): from x, y (the forward's output: the last layer's ReLU mask; the hidden activations are recomputed) and
+ *   gy (same layout as y): gW_l / gb_l are written, or added to when accumulate != 0. x is data: no gradient is formed for it.
+ *   Per-workgroup partials in `workspace` (p2c_relu_stack_workspace_floats floats, nothing in it is read before it is written)
+ *   are added in a fixed order: no float atomics, two runs give the same bits.
+ * p2c_relu_stack_supported: 1 when the widths fit -- the zero-padded weight images plus the tile activations of the backward in
+ *   160 KiB of LDS and at most 96 16x16 weight-gradient tiles (the exact rule is in the kernel file's header). Unsupported widths
+ *   make _fwd / _bwd return P2C_E_SHAPE with nothing launched. Any B >= 0, T >= 1. */
+#define P2C_RELU_STACK_MAX_LAYERS 5
+typedef struct p2c_relu_stack_desc {
+  int32_t n_layers;
+  int32_t dims[P2C_RELU_STACK_MAX_LAYERS + 1];
+  int32_t B, T, flip;
+  const float *x;
+  const float *W[P2C_RELU_STACK_MAX_LAYERS], *b[P2C_RELU_STACK_MAX_LAYERS];
+  float *y;
+  const float *gy;
+  float *gW[P2C_RELU_STACK_MAX_LAYERS], *gb[P2C_RELU_STACK_MAX_LAYERS];
+  int32_t accumulate;
+  float *workspace;
+} p2c_relu_stack_desc;
+P2C_API int p2c_relu_stack_supported(const p2c_relu_stack_desc *desc);
+P2C_API int64_t p2c_relu_stack_workspace_floats(const p2c_relu_stack_desc *desc);
+P2C_API int p2c_relu_stack_fwd(const p2c_relu_stack_desc *desc, void *stream);
+P2C_API int p2c_relu_stack_bwd(const p2c_relu_stack_desc *desc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

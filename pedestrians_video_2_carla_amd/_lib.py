@@ -121,6 +121,17 @@ class CollateDesc(ctypes.Structure):
                 ('shift', _f32p), ('scale', _f32p), ('bboxes_out', _f32p)]
 
 
+P2C_RELU_STACK_MAX_LAYERS = 5
+
+
+class ReluStackDesc(ctypes.Structure):
+    """p2c_relu_stack_desc (include/p2c.h)."""
+    _fields_ = [('n_layers', _i32), ('dims', _i32 * (P2C_RELU_STACK_MAX_LAYERS + 1)), ('B', _i32), ('T', _i32), ('flip', _i32),
+                ('x', _f32p), ('W', _f32p * P2C_RELU_STACK_MAX_LAYERS), ('b', _f32p * P2C_RELU_STACK_MAX_LAYERS), ('y', _f32p),
+                ('gy', _f32p), ('gW', _f32p * P2C_RELU_STACK_MAX_LAYERS), ('gb', _f32p * P2C_RELU_STACK_MAX_LAYERS),
+                ('accumulate', _i32), ('workspace', _f32p)]
+
+
 SYMBOLS = {
     'p2c_version': (ctypes.c_char_p, []),
     'p2c_pose_head_workspace_floats': (_i64, [_i32]),
@@ -205,6 +216,10 @@ SYMBOLS = {
     'p2c_count_target_pairs': (ctypes.c_int, [ctypes.POINTER(PoseHeadDesc), _vp, _vp]),
     'p2c_train_step_set_stream_min_batch': (ctypes.c_int, [ctypes.c_int32]),
     'p2c_train_step_set_wgrad_stream_min_batch': (ctypes.c_int, [ctypes.c_int32]),
+    'p2c_relu_stack_supported': (ctypes.c_int, [ctypes.POINTER(ReluStackDesc)]),
+    'p2c_relu_stack_workspace_floats': (_i64, [ctypes.POINTER(ReluStackDesc)]),
+    'p2c_relu_stack_fwd': (ctypes.c_int, [ctypes.POINTER(ReluStackDesc), _vp]),
+    'p2c_relu_stack_bwd': (ctypes.c_int, [ctypes.POINTER(ReluStackDesc), _vp]),
 }
 
 _lib = None

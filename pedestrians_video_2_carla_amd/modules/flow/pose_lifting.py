@@ -22,10 +22,11 @@ from pedestrians_video_2_carla_amd.modules.flow.base import LitBaseFlow
 from pedestrians_video_2_carla_amd.modules.flow.output_types import MovementsModelOutputType, TrajectoryModelOutputType
 from pedestrians_video_2_carla_amd.modules.layers.projection import ProjectionModule
 from pedestrians_video_2_carla_amd.modules.movements.baseline_3d_pose import Baseline3DPose, Baseline3DPoseRot
+from pedestrians_video_2_carla_amd.modules.movements.linear import Linear
 from pedestrians_video_2_carla_amd.modules.movements.linear_ae import LinearAE, LinearAEResidual, LinearAEResidualLeaky
 from pedestrians_video_2_carla_amd.modules.movements.lstm import LSTM
-from pedestrians_video_2_carla_amd.modules.movements.seq2seq import (Seq2Seq, Seq2SeqEmbeddings, Seq2SeqResidualA, Seq2SeqResidualB,
-                                                                   Seq2SeqResidualC)
+from pedestrians_video_2_carla_amd.modules.movements.seq2seq import (Seq2Seq, Seq2SeqEmbeddings, Seq2SeqFlatEmbeddings, Seq2SeqResidualA,
+                                                                   Seq2SeqResidualB, Seq2SeqResidualC)
 from pedestrians_video_2_carla_amd.modules.movements.pose_former import PoseFormer
 from pedestrians_video_2_carla_amd.modules.movements.zero import ZeroMovements
 from pedestrians_video_2_carla_amd.modules.trajectory.zero import ZeroTrajectory
@@ -56,8 +57,8 @@ class LitPoseLiftingFlow(LitBaseFlow):
     @classmethod
     def get_available_models(cls) -> Dict[str, Dict[str, torch.nn.Module]]:
         return {
-            'movements': {m.__name__: m for m in [ZeroMovements, LinearAE, Seq2Seq, Seq2SeqEmbeddings, Seq2SeqResidualA,
-                                                  Seq2SeqResidualB, Seq2SeqResidualC, LinearAEResidual,
+            'movements': {m.__name__: m for m in [ZeroMovements, Linear, LinearAE, Seq2Seq, Seq2SeqEmbeddings, Seq2SeqFlatEmbeddings,
+                                                  Seq2SeqResidualA, Seq2SeqResidualB, Seq2SeqResidualC, LinearAEResidual,
                                                   LinearAEResidualLeaky, PoseFormer, LSTM, Baseline3DPose,
                                                   Baseline3DPoseRot]},
             'trajectory': {m.__name__: m for m in [ZeroTrajectory]},

@@ -1,2 +1,3 @@
+from .linear import Linear  # noqa: F401
 from .lstm import LSTM  # noqa: F401
 from .transformers import SimpleTransformer  # noqa: F401

@@ -2318,3 +2318,139 @@ def post_norm_encoder_layer(x: Tensor, layer, heads: int, drop_state: Optional[T
         x, int(heads), float(layer.norm1.eps), float(layer.norm2.eps), probs, drop_state, int(site), sa.in_proj_weight,
         sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias, layer.norm1.weight, layer.norm1.bias, layer.linear1.weight,
         layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, layer.norm2.weight, layer.norm2.bias)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# fused ReLU stack (K21, csrc/p2c_relu_stack.hip): the front end of Seq2SeqFlatEmbeddings
+# ----------------------------------------------------------------------------------------------------------------------
+def _relu_stack_desc(dims: Sequence[int], B: int = 1, T: int = 1, flip: bool = False):
+    d = _lib.ReluStackDesc()
+    d.n_layers = len(dims) - 1
+    for i, v in enumerate(dims):
+        d.dims[i] = int(v)
+    d.B, d.T, d.flip = int(B), int(T), int(bool(flip))
+    return d
+
+
+def relu_stack_supported(dims: Sequence[int]) -> bool:
+    """Widths K21 covers: 1..5 layers whose zero-padded weight images and tile activations fit the 160 KiB of LDS and whose
+    weight gradient is at most 96 16x16 tiles (p2c_relu_stack_supported; the exact rule is in csrc/p2c_relu_stack.hip)."""
+    if not 2 <= len(dims) <= _lib.P2C_RELU_STACK_MAX_LAYERS + 1:
+        return False
+    return bool(_lib.lib().p2c_relu_stack_supported(ctypes.byref(_relu_stack_desc(dims))))
+
+
+class ReluStackFunction(torch.autograd.Function):
+    """y (T,B,dims[L]) = relu(W_{L-1} ... relu(W_0 x + b_0) ... + b_{L-1}) of the batch-first frames x (B,T,dims[0]), written
+    sequence-first and time-reversed with ``flip`` -- one launch forward, two backward (K21). The backward recomputes the hidden
+    activations and takes the last ReLU's mask from y. x is data: no gradient is formed for it. Inside ``grad_sinks`` the weight
+    and bias gradients are ADDED straight into ``param.grad`` (all parameters or none) and None is returned to autograd."""
+
+    @staticmethod
+    def forward(ctx, x, flip: bool, n_layers: int, *params):
+        lib = _lib.lib()
+        x = _require_device(x, 'x')
+        weights = [_require_device(p, 'weight') for p in params[:n_layers]]
+        biases = [_require_device(p, 'bias') for p in params[n_layers:]]
+        if x.ndim != 3:
+            raise RuntimeError('relu_stack: x should be (B, T, features)')
+        B, T, n0 = x.shape
+        dims = [n0] + [w.shape[0] for w in weights]
+        for l, (w, b) in enumerate(zip(weights, biases)):
+            if tuple(w.shape) != (dims[l + 1], dims[l]) or tuple(b.shape) != (dims[l + 1],):
+                raise RuntimeError('relu_stack: layer shapes do not chain')
+        desc = _relu_stack_desc(dims, B, T, flip)
+        if not lib.p2c_relu_stack_supported(ctypes.byref(desc)):
+            raise _lib.P2CError(f'relu_stack: widths {dims} are outside the fused kernel (ops.relu_stack_supported)')
+        y = torch.empty(T, B, dims[-1], dtype=torch.float32, device=x.device)
+        desc.x, desc.y = x.data_ptr(), y.data_ptr()
+        for l in range(n_layers):
+            desc.W[l], desc.b[l] = weights[l].data_ptr(), biases[l].data_ptr()
+        with torch.cuda.device(x.device):
+            _lib.check(lib.p2c_relu_stack_fwd(ctypes.byref(desc), _stream()), 'p2c_relu_stack_fwd')
+        ctx.save_for_backward(x, y, *weights, *biases)
+        ctx.params = params
+        ctx.dims, ctx.flip, ctx.n_layers = dims, bool(flip), n_layers
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        lib = _lib.lib()
+        n = ctx.n_layers
+        x, y, *rest = ctx.saved_tensors
+        weights, biases = rest[:n], rest[n:]
+        gy = _require_device(gy, 'grad')
+        B, T = x.shape[:2]
+        desc = _relu_stack_desc(ctx.dims, B, T, ctx.flip)
+        sinks = [_sink(p) for p in ctx.params]
+        if any(s is None or not s.is_contiguous() for s in sinks):
+            sinks = None
+        if sinks is not None:
+            gws, gbs = sinks[:n], sinks[n:]
+        else:
+            gws, gbs = [torch.empty_like(w) for w in weights], [torch.empty_like(b) for b in biases]
+        desc.x, desc.y, desc.gy, desc.accumulate = x.data_ptr(), y.data_ptr(), gy.data_ptr(), int(sinks is not None)
+        for l in range(n):
+            desc.W[l], desc.b[l] = weights[l].data_ptr(), biases[l].data_ptr()
+            desc.gW[l], desc.gb[l] = gws[l].data_ptr(), gbs[l].data_ptr()
+        ws = torch.empty(max(1, lib.p2c_relu_stack_workspace_floats(ctypes.byref(desc))), dtype=torch.float32, device=x.device)
+        desc.workspace = ws.data_ptr()
+        with torch.cuda.device(x.device):
+            _lib.check(lib.p2c_relu_stack_bwd(ctypes.byref(desc), _stream()), 'p2c_relu_stack_bwd')
+        if sinks is not None:
+            return (None,) * (3 + 2 * n)
+        return (None, None, None, *gws, *gbs)
+
+
+def relu_stack(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Tensor], flip: bool = False) -> Tensor:
+    """K21: ``relu(Linear_{L-1}(... relu(Linear_0(x))))`` of the batch-first x (B,T,F) as the SEQUENCE-FIRST (T,B,E) tensor an
+    LSTM encoder reads, time-reversed with ``flip``. Raises for widths outside ``relu_stack_supported`` -- the caller composes
+    those from ``dense_chain``; there is no framework fallback here."""
+    if x.requires_grad:
+        raise RuntimeError('relu_stack: x is treated as data (no input gradient is formed); use dense_chain for a differentiable input')
+    return ReluStackFunction.apply(x, bool(flip), len(weights), *weights, *biases)
+
+
+class DenseChainFunction(torch.autograd.Function):
+    """h_{l+1} = act_l(h_l W_l^T + b_l) over 2-D rows with act_l = ReLU where ``relus[l]``, as K16 launches: forward one GEMM per
+    layer with the ReLU in its epilogue (act 3 without a dropout state); backward one input-gradient GEMM per layer with the
+    previous layer's ReLU mask in ITS epilogue (act 4, aux = that layer's output) and K12 / K16-TN for the weight and bias
+    gradients (``weight_grad``: inside ``grad_sinks`` added straight into ``param.grad``). The layers K8 / K21 do not cover."""
+
+    @staticmethod
+    def forward(ctx, x, relus: Tuple[bool, ...], *params):
+        n = len(relus)
+        weights, biases = params[:n], params[n:]
+        hs = [x]
+        for l in range(n):
+            hs.append(gemm(hs[-1], weights[l], True, bias=biases[l], act=3 if relus[l] else 0))
+        ctx.save_for_backward(*hs)
+        ctx.params, ctx.relus = params, tuple(bool(r) for r in relus)
+        return hs[-1]
+
+    @staticmethod
+    def backward(ctx, gy):
+        hs, relus = ctx.saved_tensors, ctx.relus
+        n = len(relus)
+        weights, biases = ctx.params[:n], ctx.params[n:]
+        g = _require_device(gy, 'grad')
+        if relus[-1]:                                # no GEMM behind the last layer whose epilogue could carry its mask
+            g = torch.ops.aten.threshold_backward(g, hs[-1], 0.0)
+        gws, gbs, gx = [None] * n, [None] * n, None
+        for l in range(n - 1, -1, -1):
+            gws[l], gbs[l] = weight_grad(g, hs[l], weights[l], biases[l])
+            if l > 0:
+                g = gemm(g, weights[l], False, act=4 if relus[l - 1] else 0, aux=hs[l] if relus[l - 1] else None)
+            elif ctx.needs_input_grad[0]:
+                gx = gemm(g, weights[0], False)
+        return (gx, None, *gws, *gbs)
+
+
+def dense_chain(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Tensor], relus: Sequence[bool]) -> Tensor:
+    """A stack of Linear layers over the rows of the 2-D x, layer l followed by ReLU where ``relus[l]`` (K16 + K12, see
+    ``DenseChainFunction``). fp32 device tensors only: there is no framework fallback."""
+    x = _require_device(x, 'x')
+    if x.ndim != 2 or len(weights) != len(biases) or len(weights) != len(relus):
+        raise RuntimeError('dense_chain: 2-D x and one weight, bias and ReLU flag per layer expected')
+    return DenseChainFunction.apply(x, tuple(relus), *[_require_device(w, 'weight') for w in weights],
+                                    *[_require_device(b, 'bias') for b in biases])
