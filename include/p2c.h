@@ -361,7 +361,10 @@ P2C_API int p2c_lstm_steps_bwd(const p2c_lstm_desc *desc, float *workspace, void
 /* ---- Seq2Seq decoder loop (K7c) -----------------------------------------------------------------------------------------
  * for t in range(T): out_t = fc(LSTM_2layers(x_t; encoder state)); x_{t+1} = out_t   (reference seq2seq.py:245-349; the
  * decoder state is NOT carried between frames, 272-288). The caller provides the frame-invariant recurrent terms
- * k_l = b_ih_l + b_hh_l + W_hh_l hidden_l (B,4H) and the encoder cell states c_l (B,H). H = 64, O <= 64. Forward writes
+ * k_l = b_ih_l + b_hh_l + W_hh_l hidden_l (B,4H) and the encoder cell states c_l (B,H). H = 64, 1 <= O <= 160 (anything
+ * else: P2C_E_SHAPE, nothing launched). O <= 64 runs on the 16- or the 4-clip tiling (chosen by B, forced by P2C_REC_TILE, see K7b);
+ * 64 < O <= 160 has the 16-clip tiling only: P2C_REC_TILE is not read there and both of its values give the same result.
+ * Forward writes
  * out (T,B,O) and the saved activations; backward consumes g_out (T,B,O) and writes d gates0 / d gates1 (T,B,4H),
  * d out_total (T,B,O) [= g_out + the gradient that flows back through the fed-back input], and d c_l (B,H): the weight
  * gradients are dense reductions of those over all (t,b) (dW_ih0 = dgates0^T x_prev, dW_ih1 = dgates1^T h0d,

@@ -15,7 +15,9 @@
 // Backward walks t = T-1..0 with the transposed fragments, carries d x_{t+1} in registers, and writes d gates0, d gates1
 // and d out_total once: the weight gradients are then six dense library GEMMs / reductions over all (t, b) at once
 // (dW_ih0 = dgates0^T x_prev, dW_ih1 = dgates1^T h0, dW_fc = dout^T h1, dk_l = sum_t dgates_l, db_fc = sum dout).
-// H = 64, two layers, O <= 64 (pose_2d: 52); everything else takes the per-step path (ops.lstm_layer).
+// H = 64, two layers. The kernels of this file cover O <= 64 (pose_2d: 52) on both tilings; 64 < O <= 160 (absolute_loc: 78,
+// pose_changes / relative_rot: 156) runs the 16-clip kernels of p2c_s2s_wide.h, included below; everything else takes the
+// per-step path (ops.lstm_layer).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -676,6 +678,8 @@ __global__ void decoder_ghid_kernel(const float *gk, const float *w_hh, float *g
   ghid[i] = s;
 }
 
+#include "p2c_s2s_wide.h"   // 64 < O <= 160: decoder_fwd_wide_kernel / decoder_bwd_wide_kernel
+
 }  // namespace p2c_s2s
 
 using namespace p2c_s2s;
@@ -684,7 +688,7 @@ static int fill(Args &a, const p2c_decoder_desc *d) {
   if (!d || !d->c0 || !d->c1 || !d->w_ih0 || !d->w_ih1 || !d->w_fc || !d->b_fc) return P2C_E_NULL;
   if (d->hid0 ? (!d->hid1 || !d->w_hh0 || !d->w_hh1) : (!d->k0 || !d->k1)) return P2C_E_NULL;
   if ((d->g_hid0 || d->g_hid1) && (!d->g_hid0 || !d->g_hid1 || !d->w_hh0 || !d->w_hh1)) return P2C_E_NULL;
-  if (d->T < 0 || d->B < 0 || d->B > (1 << 20) || d->H != H || d->O < 1 || d->O > OMAX) return P2C_E_SHAPE;
+  if (d->T < 0 || d->B < 0 || d->B > (1 << 20) || d->H != H || d->O < 1 || d->O > OWIDE) return P2C_E_SHAPE;
   if ((d->out_bt || d->g_out_bt) && (int64_t)d->B * d->T * d->O * 4 >= (int64_t)1 << 31) return P2C_E_SHAPE;
   a = Args{};
   a.k0 = d->k0, a.c0 = d->c0, a.k1 = d->k1, a.c1 = d->c1, a.w_ih0 = d->w_ih0, a.w_ih1 = d->w_ih1, a.w_fc = d->w_fc;
@@ -723,9 +727,14 @@ static void allow_lds() {
   (void)hipFuncSetAttribute((const void *)decoder_fwd_narrow_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
   (void)hipFuncSetAttribute((const void *)decoder_bwd_narrow_kernel<13>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
   (void)hipFuncSetAttribute((const void *)decoder_bwd_narrow_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+  (void)hipFuncSetAttribute((const void *)decoder_fwd_wide_kernel<20, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+  (void)hipFuncSetAttribute((const void *)decoder_fwd_wide_kernel<40, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+  (void)hipFuncSetAttribute((const void *)decoder_bwd_wide_kernel<20, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  (void)hipFuncSetAttribute((const void *)decoder_bwd_wide_kernel<40, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   done = true;
 }
-static size_t image_bytes() { return sizeof(float) * (size_t)G4 * (H + 1); }   // the largest staged matrix (4H x H, O <= H)
+static size_t image_bytes() { return sizeof(float) * (size_t)G4 * (H + 1); }   // the largest staged block (4H x H; O <= 64: W_ih0 is no
+                                                                               // larger; O <= 160: one gate of W_ih0, 64 x 161, and W_fc, 160 x 65)
 
 extern "C" int p2c_decoder_fwd(const p2c_decoder_desc *d, void *stream) {
   Args a;
@@ -734,7 +743,7 @@ extern "C" int p2c_decoder_fwd(const p2c_decoder_desc *d, void *stream) {
   if (!a.out || !a.acts0 || !a.acts1 || !a.h0d || !a.h1) return P2C_E_NULL;
   if (a.B == 0 || a.T == 0) return 0;
   allow_lds();
-  if (use_narrow(a.B)) {
+  if (use_narrow(a.B) && a.O <= OMAX) {              // (O > 64: the 16-clip tiling only, P2C_REC_TILE is not read)
     const dim3 grid((unsigned)((a.B + NS - 1) / NS));
     if (a.O <= 52) hipLaunchKernelGGL(decoder_fwd_narrow_kernel<13>, grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
     else hipLaunchKernelGGL(decoder_fwd_narrow_kernel<16>, grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
@@ -748,7 +757,9 @@ extern "C" int p2c_decoder_fwd(const p2c_decoder_desc *d, void *stream) {
     }
     const dim3 grid((unsigned)((a.B + TS - 1) / TS));
     if (a.O <= 52) hipLaunchKernelGGL(decoder_fwd_kernel<13>, grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(decoder_fwd_kernel<16>, grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
+    else if (a.O <= OMAX) hipLaunchKernelGGL(decoder_fwd_kernel<16>, grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
+    else if (a.O <= 80) hipLaunchKernelGGL((decoder_fwd_wide_kernel<20, 2>), grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((decoder_fwd_wide_kernel<40, 3>), grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
   }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
@@ -761,14 +772,16 @@ extern "C" int p2c_decoder_bwd(const p2c_decoder_desc *d, void *stream) {
   if (!a.g_out || !a.acts0 || !a.acts1 || !a.g_gates0 || !a.g_gates1 || !a.g_outtot || !a.g_c0 || !a.g_c1) return P2C_E_NULL;
   if (a.B == 0) return 0;
   allow_lds();
-  if (use_narrow(a.B)) {
+  if (use_narrow(a.B) && a.O <= OMAX) {
     const dim3 grid((unsigned)((a.B + NS - 1) / NS));
     if (a.O <= 52) hipLaunchKernelGGL(decoder_bwd_narrow_kernel<13>, grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
     else hipLaunchKernelGGL(decoder_bwd_narrow_kernel<16>, grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
   } else {
     const dim3 grid((unsigned)((a.B + TS - 1) / TS));
     if (a.O <= 52) hipLaunchKernelGGL(decoder_bwd_kernel<13>, grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(decoder_bwd_kernel<16>, grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
+    else if (a.O <= OMAX) hipLaunchKernelGGL(decoder_bwd_kernel<16>, grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
+    else if (a.O <= 80) hipLaunchKernelGGL((decoder_bwd_wide_kernel<20, 2>), grid, dim3(256), sizeof(float) * bwd_wide_floats<2>(), (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((decoder_bwd_wide_kernel<40, 3>), grid, dim3(256), sizeof(float) * bwd_wide_floats<3>(), (hipStream_t)stream, a);
     if (a.g_hid0 && (!a.g_k0 || !a.g_k1)) return P2C_E_NULL;      // (d hid_l is formed from the stored d k_l here)
     const unsigned nk = (unsigned)(((int64_t)a.B * G4 + 255) / 256), nh = (unsigned)(((int64_t)a.B * H + 255) / 256);
     if (a.g_k0) hipLaunchKernelGGL(decoder_gk_kernel, dim3(nk), dim3(256), 0, (hipStream_t)stream, a.g_gates0, a.g_k0, a.T, a.B);

@@ -225,6 +225,10 @@ class Seq2Seq(MovementsModelOutputTypeMixin, MovementsModel):
         return self.encoder(self._format_input(x))
 
     def _decoder_loop_fusable(self, x: Tensor) -> bool:
+        """K7c takes the decoder loop for hidden_size 64, two layers and up to 160 output features: pose_2d (52), absolute_loc (78),
+        pose_changes / relative_rot (156); widths above 64 only with ``P2C_DECODER_WIDE=1`` (ops.decoder_loop_supported).
+        ``hidden_size = 128`` and absolute_loc_rot (234) are not built and stay on the per-step
+        path, as do the residual variants (they override ``_decode_frame``)."""
         from pedestrians_video_2_carla_amd import ops
         rnn = self.decoder.rnn
         return (_fused_ok(rnn, x) and rnn.bias and not rnn.bidirectional and isinstance(self.decoder.fc_out, nn.Linear)

@@ -1399,8 +1399,20 @@ def mlp_gelu(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, scale: O
 # ----------------------------------------------------------------------------------------------------------------------
 # Seq2Seq decoder loop (K7c)
 # ----------------------------------------------------------------------------------------------------------------------
+DECODER_LOOP_MAX_O = 160      # K7c: O <= 64 on both tilings, 64 < O <= 160 on the 16-clip tiling (csrc/p2c_s2s_wide.h)
+
+
 def decoder_loop_supported(hidden_size: int, num_layers: int, output_size: int) -> bool:
-    return hidden_size == 64 and num_layers == 2 and 1 <= output_size <= 64
+    """The shapes of the single-launch decoder loop (K7c): hidden size 64, two layers, 1 <= O <= 160 (pose_2d 52, absolute_loc 78,
+    pose_changes / relative_rot 156). ``hidden_size = 128`` and O > 160 (absolute_loc_rot: 234) are not built: those decoders take
+    the per-step path. 64 < O <= 160 is opt-in: ``P2C_DECODER_WIDE=1`` (read at every call) takes the fused loop, unset or ``0`` keeps
+    the per-step path -- no timing of the two arms on an MI355X is recorded yet (tools/bench_decoder_wide.py alternates them), and
+    the default moves only with such a table in DESIGN.md."""
+    if hidden_size != 64 or num_layers != 2 or not 1 <= output_size <= DECODER_LOOP_MAX_O:
+        return False
+    if output_size > 64:
+        return os.environ.get('P2C_DECODER_WIDE', '0') == '1'
+    return True
 
 
 class DecoderLoopFunction(torch.autograd.Function):
