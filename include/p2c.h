@@ -429,6 +429,19 @@ P2C_API int p2c_eval_pck(const float *pred, const float *gt, const float *mask_s
                  int32_t Jg, int32_t Cg, const int32_t *pmap, int32_t mask_missing, int32_t hips_joint, int32_t norm_mode,
                  const int32_t *hips_idx, int32_t n_hips, const int32_t *neck_idx, int32_t n_neck, float threshold,
                  float near_zero, float *partials, double *state, void *stream);
+/* p2c_eval_fb (K22): the five FB_* metrics of the pose-lifting flow (the reference package metrics/fb; the functions restated in
+ * metrics/extra_metrics.py) of one batch in one launch, ADDED to `state` (10 doubles, device): for each selected metric k,
+ * state[2k] += N * (batch mean of metric k), state[2k+1] += N -- what _FBMetric.update accumulates. `which` is a bit mask over
+ * k = 0 MPJPE, 1 weighted MPJPE, 2 N-MPJPE, 3 MPJVE (first differences over the FLATTENED frame axis, N - 1 of them), 4 PA-MPJPE
+ * (per-frame Procrustes alignment, the 3x3 problem solved in the kernel in fp64); the slots of an unselected metric are left
+ * untouched and its work is skipped. pred, gt (N,J,3) contiguous, N = B*T, J <= 64; w = J per-joint weights on the device or
+ * NULL (unit weights; then column 1 equals column 0 bit for bit). Metres in, metres out. A frame whose tensor-path value is
+ * not finite (all-zero prediction: N-MPJPE; coincident joints: PA-MPJPE) makes that column not finite here as well.
+ * P2C_E_SHAPE for J < 1, J > 64, N < 2 with MPJVE selected, `which` empty or above 31; N = 0 returns 0 and launches nothing.
+ * partials: p2c_eval_fb_workspace_floats(N) floats. */
+P2C_API int64_t p2c_eval_fb_workspace_floats(int64_t N);
+P2C_API int p2c_eval_fb(const float *pred, const float *gt, const float *w, int64_t N, int32_t J, int32_t which,
+                        float *partials, double *state, void *stream);
 
 /* ---- fused AdamW / Adam over one flat fp32 buffer ------------------------------------------------------------------
  * Replaces torch.optim.AdamW.step() as configured by the reference (modules/flow/base_model.py:156-158) when all

@@ -179,6 +179,8 @@ SYMBOLS = {
                                        ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
     'p2c_eval_pck': (ctypes.c_int, [_vp, _vp, _vp, _i64] + [ctypes.c_int32] * 4 + [_ip] + [ctypes.c_int32] * 3
                      + [_ip, ctypes.c_int32, _ip, ctypes.c_int32, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
+    'p2c_eval_fb_workspace_floats': (_i64, [_i64]),
+    'p2c_eval_fb': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     'p2c_embed_workspace_floats': (_i64, [ctypes.c_int32] * 5),
     'p2c_embed_fwd': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp] + [ctypes.c_int32] * 6 + [_vp]),
     'p2c_embed_bwd': (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp] + [ctypes.c_int32] * 6 + [_vp]),

@@ -1,16 +1,22 @@
-"""The remaining validation metrics of the reference's flows, as tensor reductions that stay
-on the batch's device: ``update`` adds into a small persistent state, nothing is read back until ``compute()``.
+"""The remaining validation metrics of the reference's flows: ``update`` adds into a small
+persistent state on the batch's device, nothing is read back until ``compute()``.
 
   MultiinputWrapper(MeanSquaredError)   metrics/multiinput_wrapper.py:9-69  (autoencoder flow's 'MSE', autoencoder.py:73-81)
   MissingJointsRatio                    metrics/missing_joints_ratio.py:9-77 (autoencoder flow's initial 'MJR', :63-71)
   FB_MPJPE / FB_WeightedMPJPE / FB_N_MPJPE / FB_MPJVE / FB_PA_MPJPE   metrics/fb/*.py (pose-lifting flow, pose_lifting.py:88-105)
 
-The first two are pinned by tests/golden/metrics_extra.npz (the reference's own classes run on two batches). The FB_*
-classes wrap ``third_party/video_pose_3d/common/loss.py`` (empty submodule in the reference checkout): the five functions
-are restated from the published VideoPose3D definitions (Pavllo et al. 2019) and are PARITY-UNPINNED; the wrappers' own
-quirks are kept -- MPJVE differentiates over the FLATTENED (clip x frame) axis, i.e. across clip boundaries
-(fb_mpjve.py:26-31), and every batch is weighted by its frame count.
+The first two are tensor reductions, pinned by tests/golden/metrics_extra.npz (the reference's own classes run on two batches).
+The FB_* classes wrap ``third_party/video_pose_3d/common/loss.py`` (empty submodule in the reference checkout): the five
+functions below are restated from the published VideoPose3D definitions (Pavllo et al. 2019) and stay PARITY-UNPINNED against
+VideoPose3D itself; the wrappers' own quirks are kept -- MPJVE differentiates over the FLATTENED (clip x frame) axis, i.e.
+across clip boundaries (fb_mpjve.py:26-31), and every batch is weighted by its frame count.
+
+On the GPU the five FB_* metrics of a batch are ONE HIP launch (K22, csrc/p2c_eval_fb.hip, through ``FBMetricSet``): a lane
+group per frame, the Procrustes problem of PA-MPJPE solved in the kernel in fp64. The kernel is pinned against the tensor
+functions of this module evaluated in fp64 (tests/test_fb_metrics_gpu.py); those functions remain the path of CPU tensors,
+fp64 or 3-D inputs, a single frame, weights that are not one value per joint, and of ``P2C_FB_FRAMEWORK=1``.
 """
+import os
 from typing import Dict, Optional, Type
 
 import torch
@@ -197,8 +203,103 @@ def p_mpjpe(predicted: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return torch.mean(torch.norm(aligned - X, dim=-1))
 
 
+_FB_SLOTS = ('FB_MPJPE', 'FB_WeightedMPJPE', 'FB_N_MPJPE', 'FB_MPJVE', 'FB_PA_MPJPE')     # column k of K22 / bit k of `which`
+
+
+class FBMetricSet:
+    """The state the FB_* metrics share: 10 doubles on the device, slots (2k, 2k + 1) = (errors, frames) of metric k, and the
+    partials buffer of K22 (csrc/p2c_eval_fb.hip). Every member is a view on its two slots. On the kernel path ONE launch per
+    batch serves all members: the first member whose ``update`` sees a batch launches for the whole set, the others' updates for
+    that batch find themselves served and do nothing; a member that comes round again (or brings other tensors) before the rest
+    have taken their turn starts the next launch. ``launches`` counts them. A stand-alone ``FB_X()`` owns a private set."""
+
+    def __init__(self):
+        self._state: Optional[torch.Tensor] = None
+        self._partials: Optional[torch.Tensor] = None
+        self._w = None                                       # (source tensor, device, J floats on the device)
+        self.members: Dict[int, '_FBMetric'] = {}
+        self.launches = 0
+        self._served = set()                                 # slots the last launch covered and that have not come for it yet
+        self._batch = None
+
+    def add(self, member: '_FBMetric'):
+        if member._slot in self.members:
+            raise ValueError(f'{_FB_SLOTS[member._slot]} is already a member of this set')
+        self.members[member._slot] = member
+
+    def _ensure(self, device):
+        if self._state is None or self._state.device != device:
+            self._state = torch.zeros(2 * len(_FB_SLOTS), dtype=torch.float64, device=device)
+        return self._state
+
+    def _weights(self, J: int, device):
+        """(usable, J fp32 weights on ``device`` or None): the kernel takes one weight per joint."""
+        member = self.members.get(1)
+        w = member.w if member is not None else None
+        if w is None:
+            return True, None
+        if w.ndim < 1 or w.shape[-1] != J or w.numel() != J:
+            return False, None
+        if self._w is None or self._w[0] is not w or self._w[1] != device:
+            self._w = (w, device, w.detach().reshape(J).to(device=device, dtype=torch.float32).contiguous())
+        return True, self._w[2]
+
+    def kernel_path(self, prediction: torch.Tensor, target: torch.Tensor) -> bool:
+        if os.environ.get('P2C_FB_FRAMEWORK', '0') == '1':
+            return False
+        if not (prediction.is_cuda and target.is_cuda and prediction.dtype == torch.float32 and target.dtype == torch.float32
+                and prediction.ndim == 4 and prediction.shape == target.shape and prediction.shape[-1] == 3):
+            return False
+        B, T, J = prediction.shape[:3]
+        return J <= 64 and B * T >= 2 and self._weights(J, prediction.device)[0]
+
+    def update(self, member: '_FBMetric', prediction: torch.Tensor, target: torch.Tensor):
+        seen = self._batch
+        if (seen is not None and member._slot in self._served and prediction is seen[0] and target is seen[1]
+                and (prediction._version, target._version) == seen[2:]):
+            self._served.discard(member._slot)
+            if not self._served:
+                self._batch = None                           # the last one served lets go of the batch
+            return
+        from pedestrians_video_2_carla_amd import _lib
+        B, T, J = prediction.shape[:3]
+        N, device = B * T, prediction.device
+        pred, gt = prediction.contiguous(), target.contiguous()
+        _, w = self._weights(J, device)
+        which = sum(1 << k for k in self.members)
+        lib = _lib.lib()
+        need = lib.p2c_eval_fb_workspace_floats(N)
+        if self._partials is None or self._partials.device != device or self._partials.numel() < need:
+            self._partials = torch.empty(need, dtype=torch.float32, device=device)
+        state = self._ensure(device)
+        with torch.cuda.device(device):
+            _lib.check(lib.p2c_eval_fb(pred.data_ptr(), gt.data_ptr(), None if w is None else w.data_ptr(), N, J, which,
+                                       self._partials.data_ptr(), state.data_ptr(),
+                                       torch.cuda.current_stream().cuda_stream), 'p2c_eval_fb')
+        self.launches += 1
+        self._served = set(self.members) - {member._slot}
+        self._batch = (prediction, target, prediction._version, target._version) if self._served else None
+
+
 class _FBMetric(_StateMetric):
-    """errors += frames * metric(batch), total += frames; compute() = 1000 * errors / total, millimetres (fb_mpjpe.py:18-41)."""
+    """errors += frames * metric(batch), total += frames; compute() = 1000 * errors / total, millimetres (fb_mpjpe.py:18-41).
+    The state is a view on two slots of an ``FBMetricSet`` (a private one unless ``metric_set`` is given). GPU fp32 batches of
+    shape (B, T, J <= 64, 3) with B * T >= 2 take K22 through the set; everything else -- CPU tensors, fp64, 3-D inputs, weights
+    that are not one value per joint, ``P2C_FB_FRAMEWORK=1`` -- runs ``_metric``, the tensor restatement, unchanged."""
+    _slot = -1
+
+    def __init__(self, metric_set: Optional[FBMetricSet] = None):
+        self._set = metric_set if metric_set is not None else FBMetricSet()
+        self._set.add(self)
+
+    @property
+    def _state(self):
+        st = self._set._state
+        return None if st is None else st[2 * self._slot:2 * self._slot + 2]
+
+    def _ensure(self, device):
+        self._set._ensure(device)
+        return self._state
 
     def _metric(self, prediction, target):
         raise NotImplementedError
@@ -209,6 +310,8 @@ class _FBMetric(_StateMetric):
         prediction, target = predictions['absolute_pose_loc'], targets['absolute_pose_loc']
         if prediction.shape != target.shape:
             return
+        if self._set.kernel_path(prediction, target):
+            return self._set.update(self, prediction, target)
         frames = float(torch.Size(prediction.shape[:-2]).numel())
         st = self._ensure(prediction.device)
         st[0] += frames * self._metric(prediction, target).double()
@@ -219,14 +322,18 @@ class _FBMetric(_StateMetric):
 
 
 class FB_MPJPE(_FBMetric):
+    _slot = 0
+
     def _metric(self, prediction, target):
         return mpjpe(prediction.reshape((-1,) + prediction.shape[-2:]), target.reshape((-1,) + target.shape[-2:]))
 
 
 class FB_WeightedMPJPE(_FBMetric):
-    def __init__(self, w: Optional[torch.Tensor] = None):
-        super().__init__()
+    _slot = 1
+
+    def __init__(self, w: Optional[torch.Tensor] = None, metric_set: Optional[FBMetricSet] = None):
         self.w = w
+        super().__init__(metric_set)
 
     def _metric(self, prediction, target):
         w = self.w if self.w is not None else torch.ones((1, 1, prediction.shape[-2]))
@@ -236,15 +343,21 @@ class FB_WeightedMPJPE(_FBMetric):
 
 
 class FB_N_MPJPE(_FBMetric):
+    _slot = 2
+
     def _metric(self, prediction, target):
         return n_mpjpe(prediction, target)                       # the 4-D (B, T, J, 3) tensors, as the reference passes them
 
 
 class FB_MPJVE(_FBMetric):
+    _slot = 3
+
     def _metric(self, prediction, target):
         return mean_velocity_error(prediction.reshape((-1,) + prediction.shape[-2:]), target.reshape((-1,) + target.shape[-2:]))
 
 
 class FB_PA_MPJPE(_FBMetric):
+    _slot = 4
+
     def _metric(self, prediction, target):
         return p_mpjpe(prediction.reshape((-1,) + prediction.shape[-2:]), target.reshape((-1,) + target.shape[-2:]))

@@ -69,15 +69,19 @@ class LitPoseLiftingFlow(LitBaseFlow):
         return {'trajectory': ZeroTrajectory, 'movements': LinearAE}
 
     def get_metrics(self):
-        """reference pose_lifting.py:88-105: MPJPE, MRPE (HIP reductions) and the five FB_* wrappers (tensor reductions on
-        the device; VideoPose3D definitions restated, parity-unpinned -- metrics/extra_metrics.py)."""
+        """reference pose_lifting.py:88-105: MPJPE, MRPE (HIP reductions) and the five FB_* wrappers. The five share one
+        ``FBMetricSet``: on the GPU a validation batch updates all of them with ONE launch (K22, csrc/p2c_eval_fb.hip), pinned
+        against the fp64 tensor restatement of the VideoPose3D definitions in metrics/extra_metrics.py (itself parity-unpinned
+        against VideoPose3D: the reference's submodule is empty)."""
         from pedestrians_video_2_carla_amd.metrics import (FB_MPJPE, FB_MPJVE, FB_N_MPJPE, FB_PA_MPJPE, FB_WeightedMPJPE, MPJPE,
-                                                         MRPE)
+                                                         MRPE, FBMetricSet)
         nodes = dict(input_nodes=self.movements_model.input_nodes, output_nodes=self.movements_model.output_nodes)
         metrics = {'MPJPE': MPJPE(**nodes), 'MRPE': MRPE(**nodes)}
         if self.movements_model.input_nodes is self.movements_model.output_nodes:     # the FB wrappers compare whole tensors
-            metrics.update({'FB_MPJPE': FB_MPJPE(), 'FB_WeightedMPJPE': FB_WeightedMPJPE(), 'FB_PA_MPJPE': FB_PA_MPJPE(),
-                            'FB_N_MPJPE': FB_N_MPJPE(), 'FB_MPJVE': FB_MPJVE()})
+            fb = FBMetricSet()
+            metrics.update({'FB_MPJPE': FB_MPJPE(metric_set=fb), 'FB_WeightedMPJPE': FB_WeightedMPJPE(metric_set=fb),
+                            'FB_PA_MPJPE': FB_PA_MPJPE(metric_set=fb), 'FB_N_MPJPE': FB_N_MPJPE(metric_set=fb),
+                            'FB_MPJVE': FB_MPJVE(metric_set=fb)})
         return metrics
 
     def _get_crucial_keys(self):

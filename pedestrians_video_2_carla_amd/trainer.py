@@ -629,6 +629,21 @@ class Trainer:
             m.repack()
         torch.cuda.synchronize()
 
+    def validate(self, flow, batches: Iterable) -> Dict[str, float]:
+        """One validation epoch over ``batches`` (Lightning's hook order: ``on_validation_batch_start`` -> ``validation_step``),
+        in eval mode and without gradients, issued eagerly; the flow's train / eval mode is put back afterwards. Returns the
+        epoch's metrics, all-reduced over the ranks (``flow.compute_metrics(sync=True)``, which also resets them)."""
+        was_training = flow.training
+        flow.eval()
+        try:
+            with torch.no_grad():
+                for i, batch in enumerate(batches):
+                    flow.on_validation_batch_start(batch, i)
+                    flow.validation_step(batch, i)
+        finally:
+            flow.train(was_training)
+        return flow.compute_metrics(sync=True)
+
     def fit(self, flow, datamodule, batches: Optional[Iterable] = None):
         self.setup(flow, datamodule)
         device = self.device or flow.device
