@@ -358,6 +358,55 @@ P2C_API int64_t p2c_lstm_steps_workspace_floats(int32_t B, int32_t H);
 P2C_API int p2c_lstm_steps_fwd(const p2c_lstm_desc *desc, void *stream);
 P2C_API int p2c_lstm_steps_bwd(const p2c_lstm_desc *desc, float *workspace, void *stream);
 
+/* ---- GRU recurrence for any hidden size (K23) -------------------------------------------------------------------------------
+ * The time loop of one torch.nn.GRU layer (gate order r, z, n), tiled and launched like K18 (one launch per time step):
+ *   r = sigmoid(gx_r + W_hr h + b_hr) ;  z = sigmoid(gx_z + W_hz h + b_hz) ;  n = tanh(gx_n + r (W_hn h + b_hn)) ;
+ *   h' = (1 - z) n + z h
+ * with gx[t] = x[t] W_ih^T + b_ih computed by the caller. b_hn sits inside the reset gate's product, so bias_hh is the kernel's
+ * and the backward writes TWO gradients: g_gx (T,B,3H) = d gx (-> dW_ih, db_ih, dx) and g_gh (T,B,3H) = d (W_hh h + b_hh), which
+ * differs from g_gx by the factor r in the n block (-> dW_hh = sum_t g_gh[t]^T h[t-1], db_hh = sum g_gh; the caller's, K12).
+ * Any 1 <= H <= 1024, B <= 2^20, 64-bit offsets. h0 = NULL is the zero state: no recurrent product at t = 0. Forward: T
+ * launches; fills out (T,B,H), optional hT (B,H) and the saved acts (T,B,4H) = r, z, n, W_hn h + b_hn (NULL: inference).
+ * Backward (descending t): g_out and g_hT are each optional; T launches plus one for g_h0 when it is asked for; `workspace` holds
+ * p2c_gru_steps_workspace_floats(B, H) floats (the carried z dh; may be NULL when T <= 1 and g_h0 is NULL), nothing in it is read
+ * before the call has written it. The fields below `g_h0` are not implemented: a descriptor that sets any of them is refused
+ * (P2C_E_SHAPE, nothing launched), as is any other H or B. */
+typedef struct p2c_gru_desc {
+  int32_t T, B, H;
+  const float *gx;              /* (T,B,3H) */
+  const float *h0;              /* (B,H) or NULL = zeros */
+  const float *w_hh;            /* (3H,H) */
+  const float *bias_hh;         /* (3H) or NULL */
+  float *out;                   /* (T,B,H) */
+  float *hT;                    /* (B,H) or NULL */
+  float *acts;                  /* (T,B,4H): written by fwd (may be NULL for inference), read by bwd */
+  const float *g_out;           /* (T,B,H) or NULL */
+  const float *g_hT;            /* (B,H) or NULL */
+  float *g_gx, *g_gh;           /* (T,B,3H) each */
+  float *g_h0;                  /* (B,H) or NULL */
+  /* the layouts of p2c_lstm_desc that a single-launch GRU would take; must be zero here: */
+  int32_t gx_bt;
+  float *out_drop;
+  int32_t *drop_state;
+  float drop_p;
+  int32_t drop_site;
+} p2c_gru_desc;
+P2C_API int64_t p2c_gru_steps_workspace_floats(int32_t B, int32_t H);
+P2C_API int p2c_gru_steps_fwd(const p2c_gru_desc *desc, void *stream);
+P2C_API int p2c_gru_steps_bwd(const p2c_gru_desc *desc, float *workspace, void *stream);
+
+/* ---- classification head (K24) -------------------------------------------------------------------------------------------
+ * One launch: mean cross-entropy of logits (B,C), 2 <= C <= 32, against int64 targets (B) (torch.nn.CrossEntropyLoss; max-
+ * subtracted log-sum-exp, fixed summation order: the same bits every run) into loss[0]; g_logits (B,C) = (softmax - onehot) /
+ * n_valid (NULL: not wanted); confusion[target][first maximal logit] += 1 in the caller's (C,C) int32 matrix (NULL: not wanted).
+ * A row whose target lies outside [0, C) is ignored everywhere (ignore_index = -100 and every other bad label): no loss, a zero
+ * gradient row, not in n_valid, not in the matrix. No valid row: loss = NaN. flags: P2C_CLS_BINARY = torch.nn.BCEWithLogitsLoss on
+ * logits (B) (C must be 1), targets 0 / 1, prediction logit > 0, a 2 x 2 matrix; P2C_CLS_COUNT_ONLY = the matrix only, loss and
+ * g_logits are neither read nor written. P2C_E_SHAPE for any other C, P2C_E_ENUM for any other flag. */
+enum { P2C_CLS_BINARY = 1, P2C_CLS_COUNT_ONLY = 2 };
+P2C_API int p2c_cls_head(const float *logits, const int64_t *targets, int64_t B, int32_t C, int32_t flags, float *loss,
+                         float *g_logits, int32_t *confusion, void *stream);
+
 /* ---- Seq2Seq decoder loop (K7c) -----------------------------------------------------------------------------------------
  * for t in range(T): out_t = fc(LSTM_2layers(x_t; encoder state)); x_{t+1} = out_t   (reference seq2seq.py:245-349; the
  * decoder state is NOT carried between frames, 272-288). The caller provides the frame-invariant recurrent terms

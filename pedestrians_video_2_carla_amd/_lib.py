@@ -85,6 +85,17 @@ class LstmDesc(ctypes.Structure):
                 ('out_drop', _f32p), ('drop_state', ctypes.c_void_p), ('drop_p', ctypes.c_float), ('drop_site', ctypes.c_int32)]
 
 
+class GruDesc(ctypes.Structure):
+    """p2c_gru_desc (include/p2c.h)."""
+    _fields_ = [('T', ctypes.c_int32), ('B', ctypes.c_int32), ('H', ctypes.c_int32), ('gx', _f32p), ('h0', _f32p),
+                ('w_hh', _f32p), ('bias_hh', _f32p), ('out', _f32p), ('hT', _f32p), ('acts', _f32p), ('g_out', _f32p),
+                ('g_hT', _f32p), ('g_gx', _f32p), ('g_gh', _f32p), ('g_h0', _f32p), ('gx_bt', ctypes.c_int32),
+                ('out_drop', _f32p), ('drop_state', ctypes.c_void_p), ('drop_p', ctypes.c_float), ('drop_site', ctypes.c_int32)]
+
+
+P2C_CLS_BINARY, P2C_CLS_COUNT_ONLY = 1, 2
+
+
 class BnormDesc(ctypes.Structure):
     """p2c_bnorm_desc (include/p2c.h)."""
     _fields_ = [('N', _i64), ('C', _i32), ('training', _i32), ('relu', _i32), ('accumulate', _i32), ('eps', ctypes.c_float),
@@ -169,6 +180,10 @@ SYMBOLS = {
     'p2c_lstm_steps_workspace_floats': (_i64, [_i32, _i32]),
     'p2c_lstm_steps_fwd': (ctypes.c_int, [ctypes.POINTER(LstmDesc), _vp]),
     'p2c_lstm_steps_bwd': (ctypes.c_int, [ctypes.POINTER(LstmDesc), _vp, _vp]),
+    'p2c_gru_steps_workspace_floats': (_i64, [_i32, _i32]),
+    'p2c_gru_steps_fwd': (ctypes.c_int, [ctypes.POINTER(GruDesc), _vp]),
+    'p2c_gru_steps_bwd': (ctypes.c_int, [ctypes.POINTER(GruDesc), _vp, _vp]),
+    'p2c_cls_head': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     'p2c_bnorm_workspace_floats': (_i64, [_i64, _i32]),
     'p2c_bnorm_fwd': (ctypes.c_int, [ctypes.POINTER(BnormDesc), _vp, _vp]),
     'p2c_bnorm_bwd': (ctypes.c_int, [ctypes.POINTER(BnormDesc), _vp, _vp]),

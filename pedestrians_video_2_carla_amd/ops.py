@@ -1121,6 +1121,191 @@ def lstm_layer(x: Tensor, h0: Optional[Tensor], c0: Optional[Tensor], w_ih: Tens
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# GRU layer: library GEMM for the input projection + one HIP launch per time step for the recurrence (K23)
+# ----------------------------------------------------------------------------------------------------------------------
+def gru_steps_supported(hidden_size: int) -> bool:
+    """The widths of the GRU recurrence (K23, p2c_gru_steps_*): any 1 <= H <= 1024."""
+    return 1 <= hidden_size <= 1024
+
+
+class GRURecurrenceFunction(torch.autograd.Function):
+    """(out (T,B,H), hT) = recurrence(gx (T,B,3H), h0, W_hh (3H,H), b_hh (3H)); gate order r, z, n (torch.nn.GRU). b_hh is the
+    recurrence's own: b_hn sits inside the reset gate's product."""
+
+    @staticmethod
+    def forward(ctx, gx, h0, w_hh, b_hh):
+        lib = _lib.lib()
+        ctx.set_materialize_grads(False)                      # an unused output (out of the last layer, hT) stays None
+        gx, w_hh = _require_device(gx, 'gx'), _require_device(w_hh, 'weight_hh')
+        ctx.zero_state = h0 is None                           # nn.GRU's default initial state: nothing to read or to return
+        ctx.has_bias, ctx.bias_param = b_hh is not None, b_hh     # (the parameter itself: its .grad may be a gradient sink)
+        T, B, G = gx.shape
+        H = w_hh.shape[1]
+        h0 = gx.new_empty(0) if ctx.zero_state else _require_device(h0, 'h0')
+        b_hh = gx.new_empty(0) if b_hh is None else _require_device(b_hh, 'bias_hh')
+        if G != 3 * H or w_hh.shape[0] != 3 * H or (not ctx.zero_state and h0.shape != (B, H)) or (ctx.has_bias and b_hh.shape != (3 * H,)):
+            raise RuntimeError(f'inconsistent GRU shapes: gx {tuple(gx.shape)}, w_hh {tuple(w_hh.shape)}, h0 {tuple(h0.shape)}')
+        if not gru_steps_supported(H):
+            raise RuntimeError(f'hidden size {H} is not supported by the HIP GRU recurrence (any 1 ... 1024)')
+        f32 = dict(dtype=torch.float32, device=gx.device)
+        out, hT, acts = torch.empty(T, B, H, **f32), torch.empty(B, H, **f32), torch.empty(T, B, 4 * H, **f32)
+        d = _lib.GruDesc()
+        d.T, d.B, d.H = T, B, H
+        d.gx, d.w_hh = gx.data_ptr(), w_hh.data_ptr()
+        if not ctx.zero_state:
+            d.h0 = h0.data_ptr()
+        if ctx.has_bias:
+            d.bias_hh = b_hh.data_ptr()
+        d.out, d.hT, d.acts = out.data_ptr(), hT.data_ptr(), acts.data_ptr()
+        with torch.cuda.device(gx.device):
+            _lib.check(lib.p2c_gru_steps_fwd(ctypes.byref(d), _stream()), 'p2c_gru_steps_fwd')
+        ctx.save_for_backward(h0, w_hh, out, acts)
+        return out, hT
+
+    @staticmethod
+    def backward(ctx, g_out, g_hT):
+        lib = _lib.lib()
+        h0, w_hh, out, acts = ctx.saved_tensors
+        T, B, H = out.shape
+        f32 = dict(dtype=torch.float32, device=out.device)
+        zero = ctx.zero_state
+        g_gx, g_gh = torch.empty(T, B, 3 * H, **f32), torch.empty(T, B, 3 * H, **f32)
+        g_h0 = None
+        d = _lib.GruDesc()
+        d.T, d.B, d.H = T, B, H
+        d.w_hh, d.acts, d.out = w_hh.data_ptr(), acts.data_ptr(), out.data_ptr()
+        if not zero:
+            g_h0 = torch.empty(B, H, **f32)
+            d.h0, d.g_h0 = h0.data_ptr(), g_h0.data_ptr()
+        d.g_out = _ptr(None if g_out is None else _require_device(g_out, 'grad out'))
+        d.g_hT = _ptr(None if g_hT is None else _require_device(g_hT, 'grad hT'))
+        d.g_gx, d.g_gh = g_gx.data_ptr(), g_gh.data_ptr()
+        with torch.cuda.device(out.device):
+            ws = torch.empty(lib.p2c_gru_steps_workspace_floats(B, H), **f32)
+            _lib.check(lib.p2c_gru_steps_bwd(ctypes.byref(d), ws.data_ptr(), _stream()), 'p2c_gru_steps_bwd')
+        g_w = g_b = None
+        if ctx.needs_input_grad[2]:       # dW_hh = sum_t g_gh[t]^T h[t-1] over all (t, b) (K12)
+            sink = _sink(w_hh)
+            g_w, acc = sink, sink is not None
+            if T > 1:
+                g_w, acc = atb(g_gh[1:].reshape(-1, 3 * H), out[:-1].reshape(-1, H), out=g_w, accumulate=acc)[0], True
+            if not zero:                  # the t = 0 term meets the initial state (zero state: no contribution)
+                g_w = atb(g_gh[0], h0, out=g_w, accumulate=acc)[0]
+            if g_w is None:
+                g_w = torch.zeros_like(w_hh)
+            if sink is not None:
+                g_w = None                # already added to w_hh.grad
+        if ctx.has_bias and ctx.needs_input_grad[3]:      # db_hh = sum over all (t, b) of g_gh, t = 0 included
+            g_b = column_sums(g_gh.view(-1, 3 * H))
+            sink = _sink(ctx.bias_param)
+            if sink is not None:
+                sink.view(-1).add_(g_b)
+                g_b = None
+        return g_gx, g_h0, g_w, g_b
+
+
+def gru_layer(x: Tensor, h0: Optional[Tensor], w_ih: Tensor, w_hh: Tensor, b_ih: Optional[Tensor],
+              b_hh: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """One unidirectional torch.nn.GRU layer: x (T,B,I) -> (out (T,B,H), hT (B,H)). The input projection x W_ih^T + b_ih for
+    all time steps is one dense GEMM; the time loop is one HIP launch per step (p2c_gru_steps_fwd, any H up to 1024), which
+    takes b_hh itself."""
+    _prefer_rocblas_once()
+    T, B, I = x.shape
+    gx = dense(x.reshape(T * B, I), w_ih, b_ih).view(T, B, -1)
+    return GRURecurrenceFunction.apply(gx, h0, w_hh, b_hh)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# classification head: loss, d logits, predicted class and confusion counts in one launch (K24)
+# ----------------------------------------------------------------------------------------------------------------------
+CLS_MAX_CLASSES = 32
+
+
+def cls_framework() -> bool:
+    """P2C_CLS_FRAMEWORK=1: the classification models run the framework RNN and the flow the torch criterion on the device (the
+    comparison arm of tools/bench_gru_classifier.py)."""
+    return os.environ.get('P2C_CLS_FRAMEWORK', '0') == '1'
+
+
+def _cls_head_ok(logits: Tensor, targets: Tensor, confusion: Optional[Tensor], binary: bool) -> bool:
+    C = 2 if binary else logits.shape[-1]
+    return (logits.is_cuda and logits.dtype == torch.float32 and targets.is_cuda and targets.dtype == torch.int64
+            and 2 <= C <= CLS_MAX_CLASSES and not cls_framework() and not torch.is_autocast_enabled()
+            and (confusion is None or (confusion.is_cuda and confusion.dtype == torch.int32 and confusion.is_contiguous()
+                                       and confusion.shape == (C, C))))
+
+
+def _count_confusion(logits: Tensor, targets: Tensor, confusion: Tensor, binary: bool) -> None:
+    """The tensor-op confusion count (host tensors, C > 32, other dtypes): same rule as K24."""
+    C = confusion.shape[0]
+    with torch.no_grad():
+        pred = (logits.reshape(-1) > 0).long() if binary else logits.argmax(dim=-1)
+        t = targets.reshape(-1).long()
+        ok = (t >= 0) & (t < C)
+        counts = torch.bincount(t[ok] * C + pred[ok], minlength=C * C).view(C, C)
+        confusion += counts.to(confusion.dtype)
+
+
+class ClassificationHeadFunction(torch.autograd.Function):
+    """loss = K24(logits, targets); the launch leaves d loss / d logits, the backward multiplies it by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, confusion, binary: bool):
+        lib = _lib.lib()
+        x = logits.contiguous()
+        B = targets.numel()
+        C = 1 if binary else x.shape[-1]
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        g = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        with torch.cuda.device(x.device):
+            _lib.check(lib.p2c_cls_head(x.data_ptr(), targets.data_ptr(), B, C, _lib.P2C_CLS_BINARY if binary else 0,
+                                        loss.data_ptr(), _ptr(g), _ptr(confusion), _stream()), 'p2c_cls_head')
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        g, = ctx.saved_tensors
+        return (None if g is None else g * g_loss), None, None, None
+
+
+def classification_loss(logits: Tensor, targets: Tensor, confusion: Optional[Tensor] = None, binary: bool = False) -> Tensor:
+    """Mean ``CrossEntropyLoss`` of logits (B, C) against int64 targets (B) -- ``binary``: ``BCEWithLogitsLoss`` of logits (B) or
+    (B, 1) against targets 0 / 1 -- and, when ``confusion`` ((C, C) int32, the caller's) is given,
+    ``confusion[target, predicted] += 1`` for every row, in one launch (K24). Rows whose target lies outside [0, C) are ignored.
+    C > 32, host tensors and other dtypes take the torch criterion plus a tensor-op count."""
+    if binary and logits.ndim == 2 and logits.shape[1] == 1:
+        logits = logits.squeeze(1)
+    targets = targets.reshape(-1)
+    if logits.shape[0] != targets.shape[0] or logits.ndim != (1 if binary else 2):
+        raise RuntimeError(f'classification_loss: logits {tuple(logits.shape)} against targets {tuple(targets.shape)}')
+    if _cls_head_ok(logits, targets, confusion, binary):
+        return ClassificationHeadFunction.apply(logits, targets.contiguous(), confusion, binary)
+    if binary:
+        loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, targets.to(logits.dtype))
+    else:
+        loss = torch.nn.functional.cross_entropy(logits, targets.long())
+    if confusion is not None:
+        _count_confusion(logits, targets, confusion, binary)
+    return loss
+
+
+def classification_count(logits: Tensor, targets: Tensor, confusion: Tensor, binary: bool = False) -> None:
+    """``confusion[target, predicted] += 1`` alone (K24's count-only mode: no loss, no gradient)."""
+    if binary and logits.ndim == 2 and logits.shape[1] == 1:
+        logits = logits.squeeze(1)
+    targets = targets.reshape(-1)
+    if _cls_head_ok(logits, targets, confusion, binary):
+        x, t = logits.detach().contiguous(), targets.contiguous()
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().p2c_cls_head(x.data_ptr(), t.data_ptr(), t.numel(), 1 if binary else x.shape[-1],
+                                               _lib.P2C_CLS_COUNT_ONLY | (_lib.P2C_CLS_BINARY if binary else 0), None, None,
+                                               confusion.data_ptr(), _stream()), 'p2c_cls_head')
+    else:
+        _count_confusion(logits, targets, confusion, binary)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # weight / bias gradient of a dense layer over many rows (K12)
 # ----------------------------------------------------------------------------------------------------------------------
 GRAD_SINKS = False      # inside ``grad_sinks(True)`` (the flat trainer's step): weight gradients may be ADDED straight into an
