@@ -163,6 +163,10 @@ __global__ __launch_bounds__(THREADS) void stats_finalize_kernel(const Args a) {
     for (int s = wave; s < a.slabs; s += WAVES) {
       const float nb = (float)((int64_t)s * a.slab_rows + a.slab_rows <= a.N ? a.slab_rows : a.N - (int64_t)s * a.slab_rows);
       const float mb = a.part[(int64_t)s * a.C + c], m2b = a.part[((int64_t)a.slabs + s) * a.C + c];
+      if (n == 0.f) {      // a wave's first slab is taken as it is: combined with the empty (0, 0, 0), (mb - 0)^2 * 0 is inf * 0 once
+        n = nb, mean = mb, m2 = m2b;      // mb^2 leaves fp32 (|mean| > 1.8e19); the same bits otherwise
+        continue;
+      }
       const float nn = n + nb, d = mb - mean;
       mean = fmaf(d, nb / nn, mean);
       m2 = m2 + m2b + d * d * (n * nb / nn);
