@@ -407,6 +407,39 @@ enum { P2C_CLS_BINARY = 1, P2C_CLS_COUNT_ONLY = 2 };
 P2C_API int p2c_cls_head(const float *logits, const int64_t *targets, int64_t B, int32_t C, int32_t flags, float *loss,
                          float *g_logits, int32_t *confusion, void *stream);
 
+/* ---- ranking metrics: AUROC, ROC and precision / recall curves (K25) -----------------------------------------------------
+ * scores (N,C) float row-major, 1 <= C <= 32, targets (N) int32, N <= 2^24. Class c is ranked one-vs-rest: a row is positive when
+ * target == c; with C == 1 the labels are 0 / 1 and a row is positive when target == 1. A row whose target lies outside [0, C)
+ * ([0, 2) for C == 1), or that holds a NaN score in any column, is dropped everywhere; n_valid[0] = rows kept. Per class, the kept
+ * rows sorted by score, descending; equal scores (-0.0 == +0.0) form one group; for group k, in order: thresholds[c][k] = its
+ * score, tps[c][k] / fps[c][k] = positives / negatives with score >= it (scikit-learn's _binary_clf_curve). n_points[c] groups,
+ * n_pos[c] = positives kept, auroc[c] = sum_k (fps[k] - fps[k-1]) (tps[k] + tps[k-1]) / (2 P Q) with the sum in 64-bit integers and
+ * one fp64 division; NaN when P == 0 or Q == 0. Entries of a row past n_points[c] are not written. All outputs are the caller's.
+ * N <= 16384: one launch, one workgroup per class sorting in LDS, no workspace (may be NULL). Larger N, or P2C_RANK_GLOBAL: a radix
+ * sort in `workspace` (p2c_rank_workspace_bytes(N, C, flags) bytes, nothing in it is read before the call has written it), 29
+ * launches, the same output bits. N == 0: no launch, n_points = n_pos = n_valid = 0, auroc = NaN. P2C_E_SHAPE for any other N or C,
+ * P2C_E_ENUM for any other flag (p2c_rank_workspace_bytes returns the same codes), P2C_E_NULL for a missing pointer. */
+enum { P2C_RANK_GLOBAL = 1 };
+typedef struct p2c_rank_desc {
+  int64_t N;
+  int32_t C, flags;
+  const float *scores;          /* (N,C) */
+  const int32_t *targets;       /* (N) */
+  float *thresholds;            /* (C,N) */
+  int32_t *tps, *fps;           /* (C,N) each */
+  int32_t *n_points, *n_pos;    /* (C) each */
+  double *auroc;                /* (C) */
+  int32_t *n_valid;             /* (1) */
+} p2c_rank_desc;
+P2C_API int64_t p2c_rank_workspace_bytes(int64_t N, int32_t C, int32_t flags);
+P2C_API int p2c_rank_curves(const p2c_rank_desc *desc, void *workspace, void *stream);
+/* One launch: logits (B,C) + int64 targets (B) -> fp32 scores and int32 targets at rows [row_offset, row_offset + B) of epoch
+ * buffers of `capacity` rows (row_offset + B > capacity: P2C_E_SHAPE). scores = softmax with the maximum subtracted, 2 <= C <= 32;
+ * flags = P2C_CLS_BINARY (C must be 1): sigmoid(logit) formed from exp(-|x|) as K24 forms it. A target outside [0, C) ([0, 2)
+ * binary) is written as -1. Rows outside the range are not touched. */
+P2C_API int p2c_rank_scores(const float *logits, const int64_t *targets, int64_t B, int32_t C, int32_t flags, float *out_scores,
+                            int32_t *out_targets, int64_t row_offset, int64_t capacity, void *stream);
+
 /* ---- Seq2Seq decoder loop (K7c) -----------------------------------------------------------------------------------------
  * for t in range(T): out_t = fc(LSTM_2layers(x_t; encoder state)); x_{t+1} = out_t   (reference seq2seq.py:245-349; the
  * decoder state is NOT carried between frames, 272-288). The caller provides the frame-invariant recurrent terms

@@ -94,6 +94,14 @@ class GruDesc(ctypes.Structure):
 
 
 P2C_CLS_BINARY, P2C_CLS_COUNT_ONLY = 1, 2
+P2C_RANK_GLOBAL = 1
+P2C_RANK_MAX_CLASSES, P2C_RANK_MAX_ROWS, P2C_RANK_LDS_ROWS = 32, 1 << 24, 16384
+
+
+class RankDesc(ctypes.Structure):
+    """p2c_rank_desc (include/p2c.h)."""
+    _fields_ = [('N', ctypes.c_int64), ('C', ctypes.c_int32), ('flags', ctypes.c_int32)] + [
+        (n, _f32p) for n in ('scores', 'targets', 'thresholds', 'tps', 'fps', 'n_points', 'n_pos', 'auroc', 'n_valid')]
 
 
 class BnormDesc(ctypes.Structure):
@@ -184,6 +192,9 @@ SYMBOLS = {
     'p2c_gru_steps_fwd': (ctypes.c_int, [ctypes.POINTER(GruDesc), _vp]),
     'p2c_gru_steps_bwd': (ctypes.c_int, [ctypes.POINTER(GruDesc), _vp, _vp]),
     'p2c_cls_head': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'p2c_rank_workspace_bytes': (_i64, [_i64, _i32, _i32]),
+    'p2c_rank_curves': (ctypes.c_int, [ctypes.POINTER(RankDesc), _vp, _vp]),
+    'p2c_rank_scores': (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _i64, _vp]),
     'p2c_bnorm_workspace_floats': (_i64, [_i64, _i32]),
     'p2c_bnorm_fwd': (ctypes.c_int, [ctypes.POINTER(BnormDesc), _vp, _vp]),
     'p2c_bnorm_bwd': (ctypes.c_int, [ctypes.POINTER(BnormDesc), _vp, _vp]),

@@ -20,8 +20,25 @@ all-reduces it over the ranks, derives on the host, and resets it:
   'none' with num_classes == 2 reports the positive class (index 1), as the reference's ``_unwrap_nested_metrics`` does;
   ``classification_average='benchmark'`` = Accuracy 'micro', Precision / Recall / F1Score 'none'.
 
-Not registered: AUROC, ROCCurve, PRCurve (the reference only logs the curves; they need the scores of the whole epoch), the
-initial-metrics pass, W&B tables and video logging. The graph classifiers and torch_geometric batches are out of scope, and so
+AUROC, ROCCurve, PRCurve (torchmetrics' definitions, which the reference registers) need every score of the epoch, ranked per
+class, so they cannot come from the matrix. ``validation_step`` and ``test_step`` -- the reference updates its metrics in
+``_eval_step_end`` only -- append their batch's fp32 softmax (binary: sigmoid) scores and int32 targets to a device epoch buffer
+(``ops.rank_scores``, one launch; the buffer doubles when full, is no module buffer and is not in ``state_dict``), and
+``compute_metrics`` ranks it on the device (K25, ``ops.rank_curves``): per class, one-vs-rest, the distinct scores in descending
+order with the positives ``tps`` and negatives ``fps`` at or above each (scikit-learn's ``_binary_clf_curve``). From those, on
+the host in fp64, with P = tps[-1] and Q = fps[-1]:
+
+  AUROC     sum_k (fps[k] - fps[k-1]) (tps[k] + tps[k-1]) / (2 P Q), the sum in integers; NaN for a class with P == 0 or Q == 0;
+            reported: the unweighted mean over the classes (torchmetrics' default 'macro', whatever ``classification_average``
+            is; NaN if any class is NaN), the one value for the binary form
+  ROCCurve  (fpr, tpr, thresholds) = ([0, fps / Q], [0, tps / P], [thresholds[0] + 1, thresholds...])
+  PRCurve   precision = tps / (tps + fps), recall = tps / P, both cut after the first point of full recall, reversed, with
+            (1, 0) appended; thresholds = the cut piece reversed
+  a curve is a tuple of three numpy arrays (binary form) or of three per-class lists of arrays; rows whose target lies outside
+  [0, C) or that hold a NaN score are dropped. ``classification_rank_metrics=False`` turns all of this off.
+
+Not registered: the initial-metrics pass, W&B tables and video logging (``sample_curve`` gives the 20 points per curve that the
+reference's ``_log_curve`` would log). The graph classifiers and torch_geometric batches are out of scope, and so
 is HIP-graph capture of this flow (``Trainer(use_graph=False)``).
 """
 import platform
@@ -71,9 +88,45 @@ def classification_metrics(matrix, average: Dict[str, str]) -> Dict[str, Any]:
     return out
 
 
+def rank_metrics(curves: Dict[str, Any], binary: bool) -> Dict[str, Any]:
+    """'AUROC', 'ROCCurve', 'PRCurve' (module docstring) from the output of ``ops.rank_curves``."""
+    auroc = curves['auroc'].cpu().numpy().astype(np.float64)
+    roc, pr = ([], [], []), ([], [], [])
+    with np.errstate(divide='ignore', invalid='ignore'):
+        for th, tps, fps in zip(curves['thresholds'], curves['tps'], curves['fps']):
+            th = th.cpu().numpy().astype(np.float64)
+            tps, fps = tps.cpu().numpy().astype(np.float64), fps.cpu().numpy().astype(np.float64)
+            if len(th) == 0:
+                empty = np.zeros(0)
+                for dst, v in zip(roc + pr, (empty,) * 6):
+                    dst.append(v)
+                continue
+            P, Q = tps[-1], fps[-1]
+            roc[0].append(np.concatenate([[0.0], fps / Q]))
+            roc[1].append(np.concatenate([[0.0], tps / P]))
+            roc[2].append(np.concatenate([[th[0] + 1.0], th]))
+            cut = int(np.argmax(tps == P)) + 1                           # up to the first point of full recall
+            pr[0].append(np.concatenate([(tps / (tps + fps))[:cut][::-1], [1.0]]))
+            pr[1].append(np.concatenate([(tps / P)[:cut][::-1], [0.0]]))
+            pr[2].append(th[:cut][::-1].copy())
+    if binary:
+        return {'AUROC': float(auroc[0]), 'ROCCurve': tuple(v[0] for v in roc), 'PRCurve': tuple(v[0] for v in pr)}
+    return {'AUROC': float(auroc.mean()), 'ROCCurve': roc, 'PRCurve': pr}
+
+
+def sample_curve(x, y, samples: int = 20):
+    """The points of one class's curve that the reference logs (``_log_curve``): ``x[int(len * k / samples)]`` for k < samples,
+    samples = min(samples, len(y)); two lists of floats."""
+    n = min(samples, len(y))
+    return ([float(x[int(len(x) * k / n)]) for k in range(n)], [float(y[int(len(y) * k / n)]) for k in range(n)])
+
+
 class LitClassificationFlow(LightningModuleBase):
+    rank_initial_capacity = 4096       # rows of the epoch score buffer when it is first allocated; it doubles when full
+
     def __init__(self, classification_model, classification_targets_key: str,
-                 classification_average: Union[str, Dict[str, str]] = 'macro', num_classes: int = 2, **kwargs: Any):
+                 classification_average: Union[str, Dict[str, str]] = 'macro', num_classes: int = 2,
+                 classification_rank_metrics: bool = True, **kwargs: Any):
         super().__init__()
         self.classification_model = classification_model
         self._targets_key = classification_targets_key
@@ -91,6 +144,10 @@ class LitClassificationFlow(LightningModuleBase):
         self.criterion = torch.nn.BCEWithLogitsLoss() if self._binary else torch.nn.CrossEntropyLoss()
         # confusion[target, predicted] of the running epoch, added to by every step's loss launch (K24)
         self.register_buffer('confusion', torch.zeros(num_classes, num_classes, dtype=torch.int32), persistent=False)
+        # scores and targets of the running evaluation epoch (AUROC and the curves): plain attributes, not in state_dict
+        self._rank_on = bool(classification_rank_metrics)
+        self._rank_scores = self._rank_targets = None
+        self._rank_rows = 0
         self.save_hyperparameters({'host': platform.node(), 'classification_average': self._average,
                                    **self.classification_model.hparams})
 
@@ -123,7 +180,10 @@ class LitClassificationFlow(LightningModuleBase):
 
     def get_metrics(self):
         """Names of the registered metrics and their averages (the values come from ``compute_metrics``)."""
-        return {'ConfusionMatrix': None, **self._average}
+        rank = {'AUROC': 'macro', 'ROCCurve': None, 'PRCurve': None} if self._rank_on else {}
+        return {'ConfusionMatrix': None, **self._average, **rank}
+
+    sample_curve = staticmethod(sample_curve)
 
     # ---- hooks the trainer calls -----------------------------------------------------------------------------------
     def on_train_batch_start(self, batch, batch_idx, *args, **kwargs):
@@ -139,14 +199,72 @@ class LitClassificationFlow(LightningModuleBase):
         return self._step(batch, batch_idx, 'train')
 
     def validation_step(self, batch, batch_idx):
-        return self._step(batch, batch_idx, 'val')
+        return self._rank_accumulate(self._step(batch, batch_idx, 'val'))
 
     def test_step(self, batch, batch_idx):
-        return self._step(batch, batch_idx, 'test')
+        return self._rank_accumulate(self._step(batch, batch_idx, 'test'))
+
+    def _rank_accumulate(self, outputs):
+        """Append an evaluation step's scores and targets to the epoch buffer (one launch; no host sync)."""
+        if not self._rank_on:
+            return outputs
+        from pedestrians_video_2_carla_amd import ops
+        logits = outputs['preds'][self._outputs_key]
+        target = torch.atleast_1d(outputs['targets'][self._targets_key]).reshape(-1)
+        B, C = target.shape[0], 1 if self._binary else logits.shape[-1]
+        if B == 0:
+            return outputs
+        need = self._rank_rows + B
+        if self._rank_scores is None or self._rank_scores.device != logits.device or self._rank_scores.shape[1] != C:
+            cap = max(int(self.rank_initial_capacity), 1)
+            while cap < B:
+                cap *= 2
+            self._rank_scores = torch.empty(cap, C, dtype=torch.float32, device=logits.device)
+            self._rank_targets = torch.empty(cap, dtype=torch.int32, device=logits.device)
+            self._rank_rows, need = 0, B
+        elif need > self._rank_targets.shape[0]:
+            cap = self._rank_targets.shape[0]
+            while cap < need:
+                cap *= 2
+            scores = torch.empty(cap, C, dtype=torch.float32, device=logits.device)
+            targets = torch.empty(cap, dtype=torch.int32, device=logits.device)
+            scores[:self._rank_rows] = self._rank_scores[:self._rank_rows]
+            targets[:self._rank_rows] = self._rank_targets[:self._rank_rows]
+            self._rank_scores, self._rank_targets = scores, targets
+        ops.rank_scores(logits, target, self._rank_scores, self._rank_targets, self._rank_rows, binary=self._binary)
+        self._rank_rows = need
+        return outputs
+
+    def _rank_gather(self, sync: bool):
+        """The epoch's (scores, targets), of all ranks when ``sync``: the ranks hold different numbers of rows, so the counts
+        are gathered first, then the rows padded to the largest count, and the padding trimmed. None when nobody has a row."""
+        rows = self._rank_rows
+        C = 1 if self._binary else self._num_classes
+        dev = self._rank_scores.device if self._rank_scores is not None else self.confusion.device
+        scores = self._rank_scores[:rows] if rows else torch.empty(0, C, dtype=torch.float32, device=dev)
+        targets = self._rank_targets[:rows] if rows else torch.empty(0, dtype=torch.int32, device=dev)
+        if sync and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            world = dist.get_world_size()
+            counts = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
+            dist.all_gather(counts, torch.tensor([rows], dtype=torch.int64, device=dev))
+            counts = [int(c) for c in counts]
+            most = max(counts)
+            if most == 0:
+                return None
+            ps, pt = torch.zeros(most, C, dtype=torch.float32, device=dev), torch.full((most,), -1, dtype=torch.int32, device=dev)
+            ps[:rows], pt[:rows] = scores, targets
+            all_s, all_t = [torch.empty_like(ps) for _ in range(world)], [torch.empty_like(pt) for _ in range(world)]
+            dist.all_gather(all_s, ps)
+            dist.all_gather(all_t, pt)
+            scores = torch.cat([v[:n] for v, n in zip(all_s, counts)])
+            targets = torch.cat([v[:n] for v, n in zip(all_t, counts)])
+        return (scores, targets) if targets.shape[0] else None
 
     def compute_metrics(self, reset: bool = True, sync: bool = True) -> Dict[str, Any]:
         """End of an epoch: the metrics of everything counted since the last reset (module docstring); ``sync`` all-reduces the
-        matrix over the ranks first. One host sync. Arrays ('none' with more than two classes, the matrix) come back as lists."""
+        matrix over the ranks first. Arrays ('none' with more than two classes, the matrix) come back as lists. When evaluation
+        steps accumulated scores, 'AUROC' (a float), 'ROCCurve' and 'PRCurve' (tuples of numpy arrays -- a curve has up to one
+        point per row) are added; ``sync`` gathers the ranks' rows first, ``reset`` empties the epoch buffer."""
         if sync and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             dist.all_reduce(self.confusion, op=dist.ReduceOp.SUM)
         matrix = self.confusion.cpu().numpy().astype(np.int64)
@@ -155,6 +273,13 @@ class LitClassificationFlow(LightningModuleBase):
         out = {'ConfusionMatrix': matrix.tolist()}
         for k, v in classification_metrics(matrix, self._average).items():
             out[k] = v.tolist() if isinstance(v, np.ndarray) else v
+        if self._rank_on:
+            from pedestrians_video_2_carla_amd import ops
+            epoch = self._rank_gather(sync)
+            if reset:
+                self._rank_rows = 0
+            if epoch is not None:
+                out.update(rank_metrics(ops.rank_curves(*epoch), self._binary))
         return out
 
     def check_finite(self, stage: str = 'train'):

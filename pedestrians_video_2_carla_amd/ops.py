@@ -1306,6 +1306,126 @@ def classification_count(logits: Tensor, targets: Tensor, confusion: Tensor, bin
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# ranking metrics: per-class sorted curve counts and AUROC of an epoch's scores (K25)
+# ----------------------------------------------------------------------------------------------------------------------
+def rank_framework() -> bool:
+    """P2C_RANK_FRAMEWORK=1: the ranking runs as tensor ops on the device (the comparison arm of tools/bench_rank_metrics.py)."""
+    return os.environ.get('P2C_RANK_FRAMEWORK', '0') == '1'
+
+
+def _rank_curves_tensor_ops(scores: Tensor, targets: Tensor) -> dict:
+    """K25's outputs from ``torch.sort``, a cumulative sum and the differences of the sorted values: the same integers."""
+    N, C = scores.shape
+    K = 2 if C == 1 else C
+    t = targets.long()
+    keep = (t >= 0) & (t < K) & ~torch.isnan(scores).any(dim=1)
+    s, t = scores[keep] + 0.0, t[keep]                                  # (-0.0 + 0.0 = +0.0: one group with +0.0)
+    n_valid = int(s.shape[0])
+    out = {'thresholds': [], 'tps': [], 'fps': [], 'n_points': [], 'n_pos': [], 'n_valid': n_valid}
+    auroc = []
+    for c in range(C):
+        v, order = torch.sort(s[:, c], descending=True)
+        pos = (t == (1 if C == 1 else c))[order]
+        ends = torch.ones(n_valid, dtype=torch.bool, device=s.device)
+        if n_valid > 1:
+            ends[:-1] = v[1:] != v[:-1]
+        idx = torch.nonzero(ends).reshape(-1)
+        tps = torch.cumsum(pos.long(), 0)[idx]
+        fps = idx + 1 - tps
+        P = int(tps[-1]) if n_valid else 0
+        Q = n_valid - P
+        zero = torch.zeros(1, dtype=torch.int64, device=s.device)
+        num = ((fps - torch.cat([zero, fps])[:-1]) * (tps + torch.cat([zero, tps])[:-1])).sum()
+        # the one division on the host, in Python integers: a device fp64 division of the framework need not round correctly
+        auroc.append(int(num) / (2 * P * Q) if P > 0 and Q > 0 else float('nan'))
+        out['thresholds'].append(v[idx])
+        out['tps'].append(tps.int())
+        out['fps'].append(fps.int())
+        out['n_points'].append(int(idx.numel()))
+        out['n_pos'].append(P)
+    out['auroc'] = torch.tensor(auroc, dtype=torch.float64, device=s.device)
+    return out
+
+
+def rank_curves(scores: Tensor, targets: Tensor, force_global: bool = False) -> dict:
+    """The ranking behind AUROC / ROC / precision-recall of scores (N, C) -- or (N), the binary form: one column, positive when
+    target == 1 -- against integer targets (N). Class c one-vs-rest; rows with a target outside the label range or a NaN score are
+    dropped. Returns ``thresholds`` / ``tps`` / ``fps``: per class, one tensor per list entry, the distinct scores in descending
+    order and the positives / negatives ranked at or above each (int32); ``n_points``, ``n_pos``: per-class ints; ``auroc``: (C)
+    float64 tensor, NaN for a class without positives or without negatives; ``n_valid``: rows kept. Device float32 scores with
+    C <= 32 and N <= 2^24 run K25 (one launch up to N = 16384, a radix sort beyond, or with ``force_global``), one host sync for
+    the sizes; host tensors, other shapes and P2C_RANK_FRAMEWORK=1 take the tensor-op restatement."""
+    if scores.ndim == 1:
+        scores = scores[:, None]
+    targets = targets.reshape(-1)
+    if scores.ndim != 2 or scores.shape[0] != targets.shape[0] or scores.shape[1] < 1:
+        raise RuntimeError(f'rank_curves: scores {tuple(scores.shape)} against targets {tuple(targets.shape)}')
+    N, C = scores.shape
+    if not (scores.is_cuda and targets.is_cuda and scores.dtype == torch.float32 and C <= _lib.P2C_RANK_MAX_CLASSES
+            and N <= _lib.P2C_RANK_MAX_ROWS and not rank_framework()):
+        with torch.no_grad():
+            return _rank_curves_tensor_ops(scores.detach().float(), targets)
+    lib = _lib.lib()
+    dev = scores.device
+    s, t = scores.detach().contiguous(), targets.to(torch.int32).contiguous()
+    flags = _lib.P2C_RANK_GLOBAL if force_global else 0
+    rows = max(N, 1)
+    thresholds = torch.empty(C, rows, dtype=torch.float32, device=dev)
+    counts = torch.empty(2, C, rows, dtype=torch.int32, device=dev)      # tps, fps
+    sizes = torch.empty(2 * C + 1, dtype=torch.int32, device=dev)        # n_points (C), n_pos (C), n_valid
+    auroc = torch.empty(C, dtype=torch.float64, device=dev)
+    ws_bytes = lib.p2c_rank_workspace_bytes(N, C, flags)
+    if ws_bytes < 0:
+        _lib.check(int(ws_bytes), 'p2c_rank_workspace_bytes')
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    d = _lib.RankDesc()
+    d.N, d.C, d.flags = N, C, flags
+    d.scores, d.targets, d.thresholds = s.data_ptr(), t.data_ptr(), thresholds.data_ptr()
+    d.tps, d.fps = counts[0].data_ptr(), counts[1].data_ptr()
+    d.n_points, d.n_pos, d.n_valid = sizes.data_ptr(), sizes[C:].data_ptr(), sizes[2 * C:].data_ptr()
+    d.auroc = auroc.data_ptr()
+    with torch.cuda.device(dev):
+        _lib.check(lib.p2c_rank_curves(ctypes.byref(d), _ptr(ws), _stream()), 'p2c_rank_curves')
+    host = sizes.cpu().tolist()                                          # the one host sync
+    n_points, n_pos = host[:C], host[C:2 * C]
+    return {'thresholds': [thresholds[c, :n_points[c]] for c in range(C)],
+            'tps': [counts[0, c, :n_points[c]] for c in range(C)], 'fps': [counts[1, c, :n_points[c]] for c in range(C)],
+            'n_points': n_points, 'n_pos': n_pos, 'auroc': auroc, 'n_valid': host[2 * C]}
+
+
+def rank_scores(logits: Tensor, targets: Tensor, out_scores: Tensor, out_targets: Tensor, offset: int, binary: bool = False) -> None:
+    """Rows [offset, offset + B) of the epoch buffers ``out_scores`` ((capacity, C) float32; (capacity, 1) binary) and
+    ``out_targets`` ((capacity) int32) from a batch's logits (B, C) -- binary: (B) or (B, 1) -- and integer targets (B): fp32
+    softmax with the maximum subtracted, or sigmoid; a target outside the label range arrives as -1. One launch on the device
+    (K25's ``p2c_rank_scores``, on both arms of P2C_RANK_FRAMEWORK: the switch is about the ranking); host tensors, other dtypes
+    and C > 32 take the tensor ops."""
+    if binary and logits.ndim == 2 and logits.shape[1] == 1:
+        logits = logits.squeeze(1)
+    targets = targets.reshape(-1)
+    B = targets.shape[0]
+    C = 1 if binary else logits.shape[-1]
+    if logits.shape[0] != B or logits.ndim != (1 if binary else 2):
+        raise RuntimeError(f'rank_scores: logits {tuple(logits.shape)} against targets {tuple(targets.shape)}')
+    cap = out_targets.shape[0]
+    if (out_scores.shape != (cap, C) or out_scores.dtype != torch.float32 or out_targets.dtype != torch.int32 or offset < 0
+            or offset + B > cap or not out_scores.is_contiguous() or not out_targets.is_contiguous()):
+        raise RuntimeError(f'rank_scores: rows [{offset}, {offset + B}) of buffers {tuple(out_scores.shape)} / {tuple(out_targets.shape)}')
+    if (logits.is_cuda and targets.is_cuda and out_scores.is_cuda and out_targets.is_cuda and logits.dtype == torch.float32
+            and targets.dtype == torch.int64 and (binary or 2 <= C <= _lib.P2C_RANK_MAX_CLASSES)):
+        x, t = logits.detach().contiguous(), targets.contiguous()
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().p2c_rank_scores(x.data_ptr(), t.data_ptr(), B, C, _lib.P2C_CLS_BINARY if binary else 0,
+                                                  out_scores.data_ptr(), out_targets.data_ptr(), offset, cap, _stream()),
+                       'p2c_rank_scores')
+        return
+    with torch.no_grad():
+        x, t = logits.detach().float(), targets.long()
+        out_scores[offset:offset + B] = torch.sigmoid(x)[:, None] if binary else torch.softmax(x, dim=-1)
+        K = 2 if binary else C
+        out_targets[offset:offset + B] = torch.where((t >= 0) & (t < K), t, torch.full_like(t, -1)).to(torch.int32)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # weight / bias gradient of a dense layer over many rows (K12)
 # ----------------------------------------------------------------------------------------------------------------------
 GRAD_SINKS = False      # inside ``grad_sinks(True)`` (the flat trainer's step): weight gradients may be ADDED straight into an
