@@ -101,7 +101,7 @@ __global__ __launch_bounds__(64 * WAVES) void mlp_fwd_kernel(const MlpArgs a) {
       if constexpr (S::kStatic && first) stage_issue(a.w_image, total4, wr, 0, issue_mark<S>(l + 1), issue_mark<S>(l + 2));
       TR(0, 3 + l);
       const bool last = (l == nl - 1);
-      layer_forward<P>(L, lds + sh.w_off(l), sh.ld(l), sh.dims(l), sh.dims(l + 1), !last, H + sh.h_off(l) * TP,
+      layer_forward<P, S::kStatic>(L, lds + sh.w_off(l), sh.ld(l), sh.dims(l), sh.dims(l + 1), !last, H + sh.h_off(l) * TP,
                     last ? nullptr : H + sh.h_off(l + 1) * TP, last ? a.y + row * sh.dims(l + 1) : nullptr, row_ok,
                     a.vec_y != 0);
     });
@@ -193,14 +193,14 @@ __global__ __launch_bounds__(64 * FW_WAVES) void mlp_fwd_wave_kernel(const MlpAr
       const float *in = (l & 1) ? bufB : bufA;
       float *out = (l & 1) ? bufA : bufB;
       const int n_in = sh.dims(l), n_out = sh.dims(l + 1);
-      const int ksteps = (((n_in + 1 + 3) >> 2) + 3) & ~3, ntiles = (n_out + 16) >> 4;
+      const int ksteps = fwd_ksteps<P, S::kStatic>(n_in), ntiles = (n_out + 16) >> 4;
       const float *wl = lds + sh.w_off(l);
       float *y_row = last ? a.y + row * n_out : nullptr;
       for (int nt = 0; nt < ntiles; nt += 2) {
         if (nt + 1 < ntiles)
-          layer_forward_nt<2, 1, P>(L, wl, sh.ld(l), ksteps, nt, n_out, !last, in, last ? nullptr : out, y_row, row_ok, a.vec_y != 0);
+          layer_forward_nt<2, 1, P, S::kStatic>(L, wl, sh.ld(l), ksteps, nt, n_out, !last, in, last ? nullptr : out, y_row, row_ok, a.vec_y != 0);
         else
-          layer_forward_nt<1, 1, P>(L, wl, sh.ld(l), ksteps, nt, n_out, !last, in, last ? nullptr : out, y_row, row_ok, a.vec_y != 0);
+          layer_forward_nt<1, 1, P, S::kStatic>(L, wl, sh.ld(l), ksteps, nt, n_out, !last, in, last ? nullptr : out, y_row, row_ok, a.vec_y != 0);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(64 * WAVES) void mlp_bwd_kernel(const MlpArgs a) {
           if (static_layers<S>() >= 4 && l == 2) tile_issue(a.gy, row0, a.N, sh.dims(nl), a.vec_gy != 0, gr);   // behind the image
         }
         TR(1, 3 + l);
-        layer_forward<P>(L, lds + sh.w_off(l), sh.ld(l), sh.dims(l), sh.dims(l + 1), true, H + sh.h_off(l) * TP,
+        layer_forward<P, S::kStatic>(L, lds + sh.w_off(l), sh.ld(l), sh.dims(l), sh.dims(l + 1), true, H + sh.h_off(l) * TP,
                       H + sh.h_off(l + 1) * TP, nullptr, false, false);
       });
       // the last layer's image (first use: the head of the dgrad chain) and the gy tile arrive behind the recomputation
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(64 * WAVES) void mlp_bwd_kernel(const MlpArgs a) {
     for_layers_down(sh, nl - 1, 1, [&](int l) {
       lds_barrier();
       TR(1, 12 + l);
-      layer_dgrad<P>(L, lds + sh.w_off(l), sh.ld(l), sh.dims(l), sh.dims(l + 1), G + sh.h_off(l + 1) * TP, H + sh.h_off(l) * TP,
+      layer_dgrad<P, S::kStatic>(L, lds + sh.w_off(l), sh.ld(l), sh.dims(l), sh.dims(l + 1), G + sh.h_off(l + 1) * TP, H + sh.h_off(l) * TP,
                   G + sh.h_off(l) * TP);
     });
     lds_barrier();

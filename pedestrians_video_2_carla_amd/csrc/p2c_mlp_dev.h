@@ -150,6 +150,14 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// The same for ONE wave: rows this wave wrote are read back by this wave (other lanes). LDS operations of a wave execute in
+// issue order; the fences keep the compiler from moving the reads above the writes.
+__device__ __forceinline__ void lds_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+}
+
 // Workgroup copy of the packed image HBM -> LDS, split into ISSUE (all global loads of the thread in flight at once:
 // the image was written by another XCD's pack kernel, so every load is an L2 miss of a few thousand cycles -- one such
 // latency is paid, not one per batch) and COMMIT (LDS stores). Round u of a thread covers float4 [u * NTH, (u+1) * NTH)
@@ -348,10 +356,29 @@ __device__ __forceinline__ void tile_commit(int n, bool vec, const TileRegs &r, 
 __device__ __forceinline__ void init_rows(float *area, int row0, int row1, int one_row) {
   for (int i = row0 * TP + threadIdx.x; i < row1 * TP; i += blockDim.x) area[i] = (i / TP == one_row) ? 1.f : 0.f;
 }
-__device__ __forceinline__ int k_rows(int n_in) { return ((((n_in + 1 + 3) >> 2) + 3) & ~3) * 4; }   // rows the k loop reads
+__device__ __forceinline__ int k_rows(int n_in) { return ((((n_in + 1 + 3) >> 2) + 3) & ~3) * 4; }   // rows behind the x tile kept finite
+// k-steps (of 4 rows each) of a layer's forward / dgrad loop. fp32 runs exactly the steps that carry data: a step beyond them
+// would add 0 * finite = +-0 to an accumulator that started at +0 and so is never -0 (round to nearest gives -0 only for
+// -0 + -0) -- the sum keeps its bits without it. Barring one case: a chain whose only non-zero products are negative and
+// underflow below the smallest denormal rounds to -0, which a padded step turned into +0 and which now stays -0. Only a
+// zero's sign changes; nothing here divides by it (relu and the masks compare with > 0).
+// The bf16 forms take whole groups of four steps (one K = 16 MFMA). EXACT is for shapes known at compile time, where the tail
+// unrolls into straight code; with run-time shapes the tail's wave-uniform branches inside the pipelined loop cost more than
+// the padded steps (K8 at 50-25-12-6-39-78-156, 131 072 rows: forward 152 -> 167 us, backward 313 -> 336 us), so those keep
+// the count rounded up to whole groups.
+template <int P, bool EXACT>
+__host__ __device__ constexpr int fwd_ksteps(int n_in) {
+  const int ks = (n_in + 1 + 3) >> 2;
+  return (P == P2C_PREC_F32 && EXACT) ? ks : (ks + 3) & ~3;
+}
+template <int P, bool EXACT>
+__host__ __device__ constexpr int dgrad_ksteps(int n_out) {
+  const int ks = (n_out + 3) >> 2;
+  return (P == P2C_PREC_F32 && EXACT) ? ks : (ks + 3) & ~3;
+}
 
 // out^T[n][s] = act( sum_k Waug[n][k] in^T_aug[k][s] ) for NT output tiles of this wave (nt0, nt0 + WAVES)
-template <int NT, int STRIDE = WAVES, int P = P2C_PREC_F32>
+template <int NT, int STRIDE = WAVES, int P = P2C_PREC_F32, bool EXACT = false>
 __device__ __forceinline__ void layer_forward_nt(const Lane &L, const float *wl, int ld, int ksteps, int nt0, int n_out,
                                                  bool relu, const float *in, float *out, float *y_row, bool row_ok,
                                                  bool vec_y) {
@@ -363,15 +390,20 @@ __device__ __forceinline__ void layer_forward_nt(const Lane &L, const float *wl,
     ap[h] = wl + ((nt0 + h * STRIDE) * 16 + L.c) * ld + L.g;
   }
   const float *bp = in + L.g * TP + L.c;
-  // Ping-pong software pipeline: the operands of k-group s+1 are in flight while the MFMAs of group s run (ksteps is a
-  // multiple of 4, >= 4). The sched_barriers keep the compiler from sinking the loads below the MFMAs they overlap.
+  // Ping-pong software pipeline: the operands of k-group s+1 are in flight while the MFMAs of group s run. With EXACT ksteps >= 1
+  // is any count: whole groups of four steps, then a tail of 1..3 steps whose operands travel with the last whole group's MFMAs;
+  // otherwise it is a multiple of four and there is no tail.
+  // The sched_barriers keep the compiler from sinking the loads below the MFMAs they overlap.
   float b0[4], a0[NT][4], b1[4], a1[NT][4];
-  auto load = [&](float (&bv)[4], float (&av)[NT][4], int s) {
+  [[maybe_unused]] const int full = ksteps & ~3, tail = ksteps & 3;
+  auto load = [&](float (&bv)[4], float (&av)[NT][4], int s, int n) {   // n: steps of this group (wave-uniform)
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      bv[u] = bp[(s + u) * 4 * TP];
+      if (u < n) {
+        bv[u] = bp[(s + u) * 4 * TP];
 #pragma unroll
-      for (int h = 0; h < NT; ++h) av[h][u] = ap[h][(s + u) * 4];
+        for (int h = 0; h < NT; ++h) av[h][u] = ap[h][(s + u) * 4];
+      }
     }
   };
   auto fma4 = [&](const float (&bv)[4], const float (&av)[NT][4]) {
@@ -386,18 +418,57 @@ __device__ __forceinline__ void layer_forward_nt(const Lane &L, const float *wl,
       for (int h = 0; h < NT; ++h) acc[h] = mfma_k16<P>(av[h], bv, acc[h]);
     }
   };
-  load(b0, a0, 0);
-  for (int s = 4;; s += 8) {
-    if (s < ksteps) load(b1, a1, s);
+  auto fma_tail = [&](const float (&bv)[4], const float (&av)[NT][4]) {   // fp32 only: the other forms have no tail
+    if constexpr (P == P2C_PREC_F32) {
+#pragma unroll
+      for (int u = 0; u < 3; ++u) {
+        if (u < tail) {
+#pragma unroll
+          for (int h = 0; h < NT; ++h) acc[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[h][u], bv[u], acc[h], 0, 0, 0);
+        }
+      }
+    }
+  };
+  if constexpr (!EXACT) {   // whole groups only (ksteps is a multiple of 4, >= 4)
+    load(b0, a0, 0, 4);
+    for (int s = 4;; s += 8) {
+      if (s < ksteps) load(b1, a1, s, 4);
+      __builtin_amdgcn_sched_barrier(0);
+      fma4(b0, a0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (s >= ksteps) break;
+      if (s + 4 < ksteps) load(b0, a0, s + 4, 4);
+      __builtin_amdgcn_sched_barrier(0);
+      fma4(b1, a1);
+      __builtin_amdgcn_sched_barrier(0);
+      if (s + 4 >= ksteps) break;
+    }
+  } else if (full == 0) {
+    load(b0, a0, 0, tail);
     __builtin_amdgcn_sched_barrier(0);
-    fma4(b0, a0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (s >= ksteps) break;
-    if (s + 4 < ksteps) load(b0, a0, s + 4);
-    __builtin_amdgcn_sched_barrier(0);
-    fma4(b1, a1);
-    __builtin_amdgcn_sched_barrier(0);
-    if (s + 4 >= ksteps) break;
+    fma_tail(b0, a0);
+  } else {
+    load(b0, a0, 0, 4);
+    for (int s = 4;; s += 8) {
+      if (s < full) load(b1, a1, s, 4);
+      else load(b1, a1, s, tail);
+      __builtin_amdgcn_sched_barrier(0);
+      fma4(b0, a0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (s >= full) {
+        fma_tail(b1, a1);
+        break;
+      }
+      if (s + 4 < full) load(b0, a0, s + 4, 4);
+      else load(b0, a0, s + 4, tail);
+      __builtin_amdgcn_sched_barrier(0);
+      fma4(b1, a1);
+      __builtin_amdgcn_sched_barrier(0);
+      if (s + 4 >= full) {
+        fma_tail(b0, a0);
+        break;
+      }
+    }
   }
 #pragma unroll
   for (int h = 0; h < NT; ++h) {
@@ -425,45 +496,82 @@ __device__ __forceinline__ void layer_forward_nt(const Lane &L, const float *wl,
 
 // in: LDS rows [k][TP] incl. ones row; out: LDS rows and/or HBM rows y. The output tiles (rows 0..n_out, ones row
 // included) are dealt round-robin to the waves.
-template <int P = P2C_PREC_F32>
+template <int P = P2C_PREC_F32, bool EXACT = false>
 __device__ __forceinline__ void layer_forward(const Lane &L, const float *wl, int ld, int n_in, int n_out, bool relu,
                                               const float *in, float *out, float *y_row, bool row_ok, bool vec_y) {
-  const int ksteps = (((n_in + 1 + 3) >> 2) + 3) & ~3;   // multiple of 4: image and activations are zero beyond n_in
+  const int ksteps = fwd_ksteps<P, EXACT>(n_in);               // image and activations are zero beyond the ones row n_in
   const int ntiles = (n_out + 16) >> 4;
   for (int nt = L.wave; nt < ntiles; nt += 2 * WAVES) {
-    if (nt + WAVES < ntiles) layer_forward_nt<2, WAVES, P>(L, wl, ld, ksteps, nt, n_out, relu, in, out, y_row, row_ok, vec_y);
-    else layer_forward_nt<1, WAVES, P>(L, wl, ld, ksteps, nt, n_out, relu, in, out, y_row, row_ok, vec_y);
+    if (nt + WAVES < ntiles) layer_forward_nt<2, WAVES, P, EXACT>(L, wl, ld, ksteps, nt, n_out, relu, in, out, y_row, row_ok, vec_y);
+    else layer_forward_nt<1, WAVES, P, EXACT>(L, wl, ld, ksteps, nt, n_out, relu, in, out, y_row, row_ok, vec_y);
   }
 }
 
 // gout^T[m][s] = (H^T[m][s] > 0 && m < n_in) * sum_k W[k][m] gin^T[k][s]; the m-tiles are dealt to the waves
-template <int P = P2C_PREC_F32>
+template <int P = P2C_PREC_F32, bool EXACT = false>
 __device__ __forceinline__ void layer_dgrad(const Lane &L, const float *wl, int ld, int n_in, int n_out, const float *gin,
                                             const float *Hprev, float *gout) {
-  const int ksteps = (((n_out + 3) >> 2) + 3) & ~3;      // multiple of 4: image rows and G rows are zero beyond n_out
+  const int ksteps = dgrad_ksteps<P, EXACT>(n_out);            // image rows and G rows are zero beyond n_out
   const int mtiles = (n_in + 15) >> 4;
+  [[maybe_unused]] const int full = ksteps & ~3, tail = ksteps & 3;
   for (int mt = L.wave; mt < mtiles; mt += WAVES) {
     f32x4 c0 = {0.f, 0.f, 0.f, 0.f};
     const float *a0p = wl + L.g * ld + mt * 16 + L.c;
     const float *bp = gin + L.g * TP + L.c;
     float b0[4], a0[4], b1[4], a1[4];
-    auto load = [&](float (&bv)[4], float (&av)[4], int s) {
+    auto load = [&](float (&bv)[4], float (&av)[4], int s, int n) {   // n: steps of this group (wave-uniform)
 #pragma unroll
-      for (int u = 0; u < 4; ++u) bv[u] = bp[(s + u) * 4 * TP], av[u] = a0p[(s + u) * 4 * ld];
+      for (int u = 0; u < 4; ++u)
+        if (u < n) bv[u] = bp[(s + u) * 4 * TP], av[u] = a0p[(s + u) * 4 * ld];
     };
     auto fma4 = [&](const float (&bv)[4], const float (&av)[4]) { c0 = mfma_k16<P>(av, bv, c0); };
-    load(b0, a0, 0);
-    for (int s = 4;; s += 8) {   // same ping-pong pipeline as layer_forward_nt
-      if (s < ksteps) load(b1, a1, s);
+    auto fma_tail = [&](const float (&bv)[4], const float (&av)[4]) {   // fp32 only: the other forms have no tail
+      if constexpr (P == P2C_PREC_F32) {
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+          if (u < tail) c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], c0, 0, 0, 0);
+      }
+    };
+    if constexpr (!EXACT) {   // whole groups only
+      load(b0, a0, 0, 4);
+      for (int s = 4;; s += 8) {   // same ping-pong pipeline as layer_forward_nt
+        if (s < ksteps) load(b1, a1, s, 4);
+        __builtin_amdgcn_sched_barrier(0);
+        fma4(b0, a0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (s >= ksteps) break;
+        if (s + 4 < ksteps) load(b0, a0, s + 4, 4);
+        __builtin_amdgcn_sched_barrier(0);
+        fma4(b1, a1);
+        __builtin_amdgcn_sched_barrier(0);
+        if (s + 4 >= ksteps) break;
+      }
+    } else if (full == 0) {
+      load(b0, a0, 0, tail);
       __builtin_amdgcn_sched_barrier(0);
-      fma4(b0, a0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (s >= ksteps) break;
-      if (s + 4 < ksteps) load(b0, a0, s + 4);
-      __builtin_amdgcn_sched_barrier(0);
-      fma4(b1, a1);
-      __builtin_amdgcn_sched_barrier(0);
-      if (s + 4 >= ksteps) break;
+      fma_tail(b0, a0);
+    } else {
+      load(b0, a0, 0, 4);
+      for (int s = 4;; s += 8) {
+        if (s < full) load(b1, a1, s, 4);
+        else load(b1, a1, s, tail);
+        __builtin_amdgcn_sched_barrier(0);
+        fma4(b0, a0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (s >= full) {
+          fma_tail(b1, a1);
+          break;
+        }
+        if (s + 4 < full) load(b0, a0, s + 4, 4);
+        else load(b0, a0, s + 4, tail);
+        __builtin_amdgcn_sched_barrier(0);
+        fma4(b1, a1);
+        __builtin_amdgcn_sched_barrier(0);
+        if (s + 4 >= full) {
+          fma_tail(b0, a0);
+          break;
+        }
+      }
     }
     const int mb = mt * 16 + 4 * L.g;
 #pragma unroll

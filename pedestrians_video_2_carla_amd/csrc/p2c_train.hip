@@ -254,19 +254,30 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
     const int64_t nxt = (int64_t)clip + gridDim.x;
     tile_issue(m.x, nxt * T, nxt < d.B ? nxt * T + T : 0, S::dims(0), true, xr);
   }
+  // Layers 1 and 2 (13 and 6 outputs) are one output tile each, both on wave 0: they run back to back behind ONE workgroup
+  // barrier, with a wave-local sync in between; layer 3's barrier publishes the rows of both. On the first clip the image
+  // rounds of layer 2 are therefore committed in front of layer 1's barrier.
+  static_assert(S::dims(2) + 1 <= 16 && S::dims(3) + 1 <= 16, "layers 1 and 2: one output tile each");
+  static_assert(rounds_upto<S>(2) <= issue_mark<S>(2), "layer 2's image rounds are in flight before layer 1's barrier commits them");
   for_layers(sh, 0, nl, [&](int ll) {
+    const bool run = ll == 2;           // second layer of the single-wave run: no workgroup barrier
 #if P2C_TRAIN_DMA_IMAGE
-    if constexpr (first) image_dma_wait(ll, L.wave);
-    lds_barrier();
+    if constexpr (first) image_dma_wait(ll == 1 ? 2 : ll, L.wave);
+    if (run) lds_wave_sync();
+    else lds_barrier();
     TT(0, 2 + ll);
 #else
-    if constexpr (first) stage_commit(total4, wr, lds, 0, ll == 0 ? 0 : rounds_upto<S>(ll - 1), rounds_upto<S>(ll));
-    lds_barrier();
+    if constexpr (first) {
+      const int upto = ll == 1 ? 2 : ll;
+      if (!run) stage_commit(total4, wr, lds, 0, ll == 0 ? 0 : rounds_upto<S>(ll - 1), rounds_upto<S>(upto));
+    }
+    if (run) lds_wave_sync();
+    else lds_barrier();
     TT(0, 2 + ll);
     if constexpr (first) stage_issue(m.w_image, total4, wr, 0, issue_mark<S>(ll + 1), issue_mark<S>(ll + 2));
 #endif
     const bool last = (ll == nl - 1);
-    layer_forward(L, lds + S::w_off(ll), S::ld(ll), S::dims(ll), S::dims(ll + 1), !last, H + S::h_off(ll) * TP,
+    layer_forward<P2C_PREC_F32, true>(L, lds + S::w_off(ll), S::ld(ll), S::dims(ll), S::dims(ll + 1), !last, H + S::h_off(ll) * TP,
                   last ? Y : H + S::h_off(ll + 1) * TP, nullptr, false, false);
   });
   lds_barrier();
@@ -328,13 +339,35 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   if (K::SCAN) {
     float *sb = plane0;
     lds_barrier();    // every group is done reading the scan planes
-    sb[(t * ph::GROUP + PL.j) * 3 + 0] = taup.x, sb[(t * ph::GROUP + PL.j) * 3 + 1] = taup.y, sb[(t * ph::GROUP + PL.j) * 3 + 2] = taup.z;
+    // Ssum[t][col] = sum_{tt >= t} taup[tt][col] on the matrix pipe: the plane is a row-major [16 frames][96 columns] matrix (78
+    // in use), Ssum = U taup with U the 0/1 upper triangle. Waves 0..4 take 16 columns each and run four dependent 16x16x4 MFMAs
+    // with k reversed (k <-> tt = 15 - k): per element the chain adds tt = 15, 14, ... t and then zeros -- the order of a loop
+    // from T - 1 down to t that starts at 0.f (rows tt >= T hold zeros; 0 * finite = +-0 leaves the sum as it is). Unlike the
+    // loop, 0 * inf = NaN reaches the frames after a non-finite one: only once the gradient is non-finite anyway.
+    constexpr int ROW = ph::GROUP * 3, SUF_TILES = (ph::J * 3 + 15) / 16;
+    static_assert(T_MAX == 16 && SUF_TILES <= WAVES && 16 * SUF_TILES <= ROW, "suffix sum over time: one 16-column tile per wave");
+    const bool live = t < T;
+    sb[(t * ph::GROUP + PL.j) * 3 + 0] = live ? taup.x : 0.f, sb[(t * ph::GROUP + PL.j) * 3 + 1] = live ? taup.y : 0.f;
+    sb[(t * ph::GROUP + PL.j) * 3 + 2] = live ? taup.z : 0.f;
     lds_barrier();
-    ph::V3 Ssum = ph::v3(0.f, 0.f, 0.f);
-    for (int tt = T - 1; tt >= t; --tt) {
-      const float *q = sb + (tt * ph::GROUP + PL.j) * 3;
-      Ssum = Ssum + ph::v3(q[0], q[1], q[2]);
+    if (L.wave < SUF_TILES) {
+      f32x4 su = {0.f, 0.f, 0.f, 0.f};
+      float bv[4], av[4];
+      int sc = L.c, sg = L.g;                                // re-made here: the triangle and the addresses depend on the lane
+      asm volatile("" : "+v"(sc), "+v"(sg));                 // alone and would otherwise be hoisted out of the clip loop (registers)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int tt = 15 - 4 * u - sg;
+        bv[u] = sb[tt * ROW + 16 * L.wave + sc], av[u] = tt >= sc ? 1.f : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) su = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], su, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) plane1[(4 * sg + r) * ROW + 16 * L.wave + sc] = su[r];
     }
+    lds_barrier();
+    const float *q = plane1 + (t * ph::GROUP + jc) * 3;      // (lanes beyond the joints read joint 0's sums and drop them)
+    const ph::V3 Ssum = ph::v3(q[0], q[1], q[2]);
     const ph::M3 Rprev = (t > 0) ? ph::mulTN(c, R) : Rref;
     g = ph::vmulT(Ssum, Rprev);
   }
@@ -368,10 +401,13 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
 
   // ---- dgrad chain G_l = relu'(H_l) .* (W_l^T G_{l+1}), l = L-1 .. 1 ----
   TT(0, 13);
+  // Steps 3 and 2 (n_in = 6 and 13) are one m-tile each, both on wave 0: one run behind step 3's barrier, wave-local sync between.
+  static_assert(S::dims(3) <= 16 && S::dims(2) <= 16, "dgrad steps 3 and 2: one m-tile each");
   for_layers_down(sh, nl - 1, 1, [&](int ll) {
-    lds_barrier();
+    if (ll == 2) lds_wave_sync();
+    else lds_barrier();
     TT(0, 14 + ll);
-    layer_dgrad(L, lds + S::w_off(ll), S::ld(ll), S::dims(ll), S::dims(ll + 1), G + S::h_off(ll + 1) * TP, H + S::h_off(ll) * TP,
+    layer_dgrad<P2C_PREC_F32, true>(L, lds + S::w_off(ll), S::ld(ll), S::dims(ll), S::dims(ll + 1), G + S::h_off(ll + 1) * TP, H + S::h_off(ll) * TP,
                 G + S::h_off(ll) * TP);
   });
   lds_barrier();

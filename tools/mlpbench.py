@@ -5,7 +5,9 @@ import torch
 from pedestrians_video_2_carla_amd import ops
 
 d = torch.device('cuda:0')
-dims = [52, 26, 13, 6, 39, 78, 156]
+dims = [52, 26, 13, 6, 39, 78, 156]             # P2C_MLPBENCH_DIMS=50-25-12-6-39-78-156: other widths (run-time shapes)
+if os.environ.get('P2C_MLPBENCH_DIMS'):
+    dims = [int(v) for v in os.environ['P2C_MLPBENCH_DIMS'].split('-')]
 torch.manual_seed(0)
 Ws = [torch.randn(o, i, device=d) * 0.1 for i, o in zip(dims[:-1], dims[1:])]
 bs = [torch.randn(o, device=d) * 0.1 for o in dims[1:]]
