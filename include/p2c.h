@@ -586,6 +586,51 @@ typedef struct p2c_collate_desc {
 } p2c_collate_desc;
 P2C_API int p2c_collate_fwd(const p2c_collate_desc *desc, void *stream);
 
+/* ---- K26: K11 over a batch whose clips come from several data skeletons, one launch -----------------------------------
+ * Replaces, in the reference, MixedDataset.__getitem__ (data/mixed/mixed_dataset.py:91-107) handing each index to the
+ * dataset it belongs to, i.e. BaseDataset.__getitem__ with that dataset's skeleton, deformation and transform. Clip n of
+ * the batch is row[n] of source source[n] and is processed exactly as K11 processes a clip of that source (same device
+ * function, same bits). The draws and side tensors are indexed by batch position; noise and miss_u have Jmax = max Jd
+ * joints per frame and a source reads its first Jd. A source whose flag is off skips that step and its reads. Clips of a
+ * source without boxes use the boxes of the pose, and bboxes_out (optional) receives their augmented pose boxes.
+ * Lane grouping as K11 (32 lanes per frame when every Jd and Ji <= 32, else 64). source[n] >= S and row[n] outside
+ * [0, n) are clamped in the kernel, never followed. Errors per source as K11's; also P2C_E_SHAPE for S outside
+ * [1, P2C_COLLATE_MAX_SOURCES] and P2C_E_NULL without source / row. N == 0 launches nothing. */
+#define P2C_COLLATE_MAX_SOURCES 4
+typedef struct p2c_collate_source {
+  int64_t n;                   /* clips stored in raw */
+  const float *raw;            /* (n,T,Jd,C) */
+  int32_t Jd, C;               /* joints of this source's skeleton (<= 64), channels 2 or 3 */
+  const int32_t *flip_perm;    /* host, Jd (needed when the batch has is_flipped) */
+  const float *miss_prob;      /* host, Jd (needed with has_miss) */
+  int32_t transform;           /* P2C_TRANSFORM_* */
+  int32_t n_hips, hips_idx[2], n_neck, neck_idx[2];
+  int32_t K;                   /* common joints with the model-input skeleton (0 = same skeleton, Ji == Jd) */
+  const int32_t *src_idx;      /* host, K */
+  const int32_t *dst_idx;      /* host, K */
+  int32_t has_noise, has_miss, has_bboxes;   /* this source's clips read noise / miss_u / bboxes */
+} p2c_collate_source;
+typedef struct p2c_collate_mixed_desc {
+  int64_t N;                   /* clips in the batch */
+  int32_t T, Ji, S;            /* frames per clip, joints of the model-input skeleton, sources */
+  int32_t return_confidence;   /* every source must have 3 channels */
+  float near_zero;
+  p2c_collate_source sources[P2C_COLLATE_MAX_SOURCES];
+  const uint8_t *source;       /* (N) source of clip n */
+  const int32_t *row;          /* (N) its row in that source's raw */
+  const uint8_t *is_flipped;   /* (N) or NULL */
+  const float *rotation_deg;   /* (N) or NULL */
+  const float *bboxes;         /* (N,T,2,2), read for clips of sources with has_bboxes */
+  const float *clip_size;      /* (N,2) or NULL; 0 = unknown */
+  const float *noise;          /* (N,T,Jmax,2), Jmax = max Jd over the sources */
+  const float *miss_u;         /* (N,T,Jmax) */
+  float *frames;               /* (N,T,Ji,return_confidence ? 3 : 2) */
+  float *t_projection_2d, *t_deformed, *t_transformed;   /* (N,T,Ji,2) or NULL */
+  float *shift, *scale;        /* (N,T,2), (N,T) or NULL */
+  float *bboxes_out;           /* (N,T,2,2) or NULL */
+} p2c_collate_mixed_desc;
+P2C_API int p2c_collate_mixed_fwd(const p2c_collate_mixed_desc *desc, void *stream);
+
 /* ---- C (+)= A^T [B | 1] over K rows (weight + bias gradient of a dense layer) ------------------------------------------------
  * Replaces, in the backward of the Seq2Seq models (modules/movements/seq2seq/seq2seq.py:36-94: the nn.LSTM projections and
  * Decoder.fc_out under autograd), the split-K library GEMM dW = dY^T X and the column reduction db = sum_rows dY.

@@ -140,6 +140,27 @@ class CollateDesc(ctypes.Structure):
                 ('shift', _f32p), ('scale', _f32p), ('bboxes_out', _f32p)]
 
 
+P2C_COLLATE_MAX_SOURCES = 4
+_fp = ctypes.POINTER(ctypes.c_float)
+
+
+class CollateSource(ctypes.Structure):
+    """p2c_collate_source (include/p2c.h)."""
+    _fields_ = [('n', _i64), ('raw', _f32p), ('Jd', _i32), ('C', _i32), ('flip_perm', _ip), ('miss_prob', _fp),
+                ('transform', _i32), ('n_hips', _i32), ('hips_idx', _i32 * 2), ('n_neck', _i32), ('neck_idx', _i32 * 2),
+                ('K', _i32), ('src_idx', _ip), ('dst_idx', _ip), ('has_noise', _i32), ('has_miss', _i32),
+                ('has_bboxes', _i32)]
+
+
+class CollateMixedDesc(ctypes.Structure):
+    """p2c_collate_mixed_desc (include/p2c.h)."""
+    _fields_ = [('N', _i64), ('T', _i32), ('Ji', _i32), ('S', _i32), ('return_confidence', _i32),
+                ('near_zero', ctypes.c_float), ('sources', CollateSource * P2C_COLLATE_MAX_SOURCES), ('source', _vp),
+                ('row', _vp), ('is_flipped', _vp), ('rotation_deg', _f32p), ('bboxes', _f32p), ('clip_size', _f32p),
+                ('noise', _f32p), ('miss_u', _f32p), ('frames', _f32p), ('t_projection_2d', _f32p), ('t_deformed', _f32p),
+                ('t_transformed', _f32p), ('shift', _f32p), ('scale', _f32p), ('bboxes_out', _f32p)]
+
+
 P2C_RELU_STACK_MAX_LAYERS = 5
 
 
@@ -183,6 +204,7 @@ SYMBOLS = {
     'p2c_mlp_image_index': (_i64, [ctypes.POINTER(MlpDesc), _ip, _i64]),
     'p2c_adamw_step': (ctypes.c_int, [ctypes.POINTER(AdamWDesc), _vp]),
     'p2c_collate_fwd': (ctypes.c_int, [ctypes.POINTER(CollateDesc), _vp]),
+    'p2c_collate_mixed_fwd': (ctypes.c_int, [ctypes.POINTER(CollateMixedDesc), _vp]),
     'p2c_lstm_rec_fwd': (ctypes.c_int, [ctypes.POINTER(LstmDesc), _vp]),
     'p2c_lstm_rec_bwd': (ctypes.c_int, [ctypes.POINTER(LstmDesc), _vp]),
     'p2c_lstm_steps_workspace_floats': (_i64, [_i32, _i32]),

@@ -15,6 +15,10 @@
 // HBM traffic is exactly the boundary tensors: the raw pose and the random draws in, six small tensors out.
 // The random numbers are inputs (the host wrapper draws them on the device): the kernel is a pure function, so the
 // reference, the oracle (oracle/collate.py) and this kernel can be compared on identical draws.
+//
+// K26 (p2c_collate_mixed_fwd) is the same frame function for a batch whose clips come from up to four data skeletons
+// (the reference's MixedDataset, data/mixed/mixed_dataset.py): the source of a clip -- raw array, joints, channels, flip
+// permutation, deformation, transform, node map -- is looked up per lane group from a table in the kernel arguments.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
@@ -45,6 +49,40 @@ struct Args {
   float miss_prob[MAXJ];
 };
 
+// K26: the per-source part of Args, S of them in the kernel-argument struct (432 bytes each)
+struct Source {
+  const float *raw;
+  int64_t rows;            // clips in raw: row[n] is clamped to it
+  int32_t Jd, C, transform, n_hips, n_neck;
+  int32_t hips_idx[2], neck_idx[2];
+  int32_t flags;           // bit 0 noise, bit 1 missing joints, bit 2 boxes given
+  int8_t perm[MAXJ];
+  int8_t inv[MAXJ];
+  float miss_prob[MAXJ];
+};
+struct MixedArgs {
+  const float *rotation, *bboxes, *clip_size, *noise, *miss_u;
+  const uint8_t *is_flipped, *source;
+  const int32_t *row;
+  float *frames, *t_projection_2d, *t_deformed, *t_transformed, *shift, *scale, *bboxes_out;
+  int64_t frames_total;
+  int32_t T, Ji, Cf, S, Jmax;
+  float near_zero;
+  Source src[P2C_COLLATE_MAX_SOURCES];
+};
+static_assert(sizeof(MixedArgs) <= 4096, "kernel arguments of collate_mixed_kernel");
+
+// What one lane group needs to know about the source of its frame. K11 fills it from Args (every field wave-uniform, so it
+// stays in SGPRs); K26 fills it per lane group from the table of its clip's source.
+struct View {
+  const float *raw, *noise, *miss_u, *bboxes;   // nullptr = that step is off for this source
+  int64_t rf;                                   // frame index in raw (K11: the batch frame)
+  int32_t Jd, Jn, C, transform, n_hips, n_neck; // Jn: joints per frame of noise / miss_u
+  int32_t hips_idx[2], neck_idx[2];
+  float mp;                                     // this lane's miss_prob, flip source joint and node-map source joint
+  int32_t perm_j, inv_j;
+};
+
 template <int G>
 __device__ __forceinline__ float gmin(float v) {
 #pragma unroll
@@ -61,10 +99,11 @@ __device__ __forceinline__ float finite_or_zero(float v) { return isfinite(v) ? 
 
 // Normalizer.__call__ (normalizer.py:20-41), dim = 2, for the frame of this lane group: (x, y[, conf]) -> normalised
 // (x, y), conf through nan_to_zero; shift / scale of the frame. Same arithmetic as p2c_aux::normalize_kernel.
+// The shuffles sit under conditions on the source's transform: uniform over a lane group, which is all they read.
 template <int G>
-__device__ __forceinline__ void normalise(const Args &a, int base, bool active, float x, float y, float conf,
-                                          float &ox, float &oy, float &oconf, float (&s)[2], float &scale) {
-  const int tr = a.transform;
+__device__ __forceinline__ void normalise(const View &v, float near_zero, int base, bool active, float x, float y,
+                                          float conf, float &ox, float &oy, float &oconf, float (&s)[2], float &scale) {
+  const int tr = v.transform;
   float k[2] = {0.f, 0.f};
   s[0] = s[1] = 0.f;
   scale = 1.f;
@@ -72,19 +111,19 @@ __device__ __forceinline__ void normalise(const Args &a, int base, bool active, 
   if (tr != P2C_TRANSFORM_BBOX) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      float h = __shfl(p[c], base + a.hips_idx[0], 64);
-      if (a.n_hips == 2) h = 0.5f * (h + __shfl(p[c], base + a.hips_idx[1], 64));
-      float q = __shfl(p[c], base + a.neck_idx[0], 64);
-      if (a.n_neck == 2) q = 0.5f * (q + __shfl(p[c], base + a.neck_idx[1], 64));
+      float h = __shfl(p[c], base + v.hips_idx[0], 64);
+      if (v.n_hips == 2) h = 0.5f * (h + __shfl(p[c], base + v.hips_idx[1], 64));
+      float q = __shfl(p[c], base + v.neck_idx[0], 64);
+      if (v.n_neck == 2) q = 0.5f * (q + __shfl(p[c], base + v.neck_idx[1], 64));
       s[c] = h, k[c] = q;
     }
     scale = sqrtf(fmaf(k[1] - s[1], k[1] - s[1], (k[0] - s[0]) * (k[0] - s[0])));
   }
   bool use_bb = false;
   if (tr == P2C_TRANSFORM_HIPS_NECK_BBOX)
-    use_bb = (s[0] < a.near_zero && s[1] < a.near_zero) || (k[0] < a.near_zero && k[1] < a.near_zero);
+    use_bb = (s[0] < near_zero && s[1] < near_zero) || (k[0] < near_zero && k[1] < near_zero);
   if (__any(tr == P2C_TRANSFORM_BBOX || use_bb)) {
-    const bool missing = !active || (x < a.near_zero && y < a.near_zero);
+    const bool missing = !active || (x < near_zero && y < near_zero);
     const float inf = __builtin_inff();
     const float mn0 = gmin<G>(missing ? inf : x), mn1 = gmin<G>(missing ? inf : y);
     const float mx0 = gmax<G>(missing ? -inf : x), mx1 = gmax<G>(missing ? -inf : y);
@@ -96,21 +135,17 @@ __device__ __forceinline__ void normalise(const Args &a, int base, bool active, 
   }
   ox = finite_or_zero((x - s[0]) / scale), oy = finite_or_zero((y - s[1]) / scale);
   oconf = finite_or_zero(conf);
-  if (a.C > 2 && !(oconf >= a.near_zero)) ox = 0.f, oy = 0.f;     // normalizer.py:35-37
+  if (v.C > 2 && !(oconf >= near_zero)) ox = 0.f, oy = 0.f;     // normalizer.py:35-37
 }
 
-template <int G>
-__global__ __launch_bounds__(256) void collate_kernel(const Args a) {
-  const int lane = threadIdx.x & 63;
-  const int j = lane & (G - 1);
-  const int base = lane & ~(G - 1);
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t f = wave * (64 / G) + (lane / G);           // frame index over N * T
-  const bool live = f < a.frames_total;
+// One frame per lane group, shared by K11 and K26. `a` carries what holds for the whole batch (draws and side tensors by
+// batch position, outputs, T, Ji, Cf, near_zero), `v` what holds for the source of this group's frame. f = batch frame,
+// n = batch clip; live = the group has a frame at all.
+template <int G, class A>
+__device__ __forceinline__ void collate_frame(const A &a, const View &v, int j, int base, int64_t f, int64_t n, bool live) {
   const int64_t fc = live ? f : 0;
-  const int64_t n = fc / a.T;
-  const bool active = live && j < a.Jd;
-  const int C = a.C;
+  const bool active = live && j < v.Jd;
+  const int C = v.C;
 
   // every HBM read of the frame goes out before the first use: one memory latency per wave, not one per stage
   float x = 0.f, y = 0.f, conf = 0.f, nx = 0.f, ny = 0.f, mu = 2.f;
@@ -118,34 +153,33 @@ __global__ __launch_bounds__(256) void collate_kernel(const Args a) {
   const bool flip = a.is_flipped && a.is_flipped[n] != 0;
   const bool rotate = a.rotation != nullptr;
   if (active) {
-    const float *p = a.raw + (fc * a.Jd + j) * C;
+    const float *p = v.raw + (v.rf * v.Jd + j) * C;
     if (C > 2) {
-      const f32x3 v = *reinterpret_cast<const f32x3 __attribute__((aligned(4))) *>(p);
-      x = v[0], y = v[1], conf = v[2];
+      const f32x3 q = *reinterpret_cast<const f32x3 __attribute__((aligned(4))) *>(p);
+      x = q[0], y = q[1], conf = q[2];
     } else {
-      const f32x2 v = ld2(p);
-      x = v[0], y = v[1];
+      const f32x2 q = ld2(p);
+      x = q[0], y = q[1];
     }
-    if (a.noise) {
-      const f32x2 q = ld2(a.noise + (fc * a.Jd + j) * 2);
+    if (v.noise) {
+      const f32x2 q = ld2(v.noise + (fc * v.Jn + j) * 2);
       nx = q[0], ny = q[1];
     }
-    if (a.miss_u) mu = a.miss_u[fc * a.Jd + j];
+    if (v.miss_u) mu = v.miss_u[fc * v.Jn + j];
   }
-  if (a.bboxes) {
-    const float *b = a.bboxes + fc * 4;
+  if (v.bboxes) {
+    const float *b = v.bboxes + fc * 4;
     bx[0] = b[0], bx[1] = b[1], bx[2] = b[2], bx[3] = b[3];
   }
   if (a.clip_size) cw = a.clip_size[2 * n], ch = a.clip_size[2 * n + 1];
   if (rotate) deg = a.rotation[n];
-  const int lj = j & (MAXJ - 1);
-  const float mp = a.miss_prob[lj];               // per-lane reads of the kernel-argument tables, also up front
-  const int perm_j = a.perm[lj], inv_j = a.inv[lj];
+  const float mp = v.mp;
+  const int perm_j = v.perm_j, inv_j = v.inv_j;
 
   // ---- AugmentPose: boxes and centres (augment_pose.py:57-60) ------------------------------------------------------
   float lo[2] = {0.f, 0.f}, hi[2] = {0.f, 0.f}, ctr[2] = {0.f, 0.f};
   if (a.is_flipped || rotate) {
-    if (a.bboxes) {
+    if (v.bboxes) {
       lo[0] = bx[0], lo[1] = bx[1], hi[0] = bx[2], hi[1] = bx[3];
     } else {                                                   // get_bboxes(pose), utils/tensors.py:12-26
       const bool missing = !active || (x < a.near_zero && y < a.near_zero);
@@ -199,18 +233,18 @@ __global__ __launch_bounds__(256) void collate_kernel(const Args a) {
   // ---- apply_deform (projection_2d_mixin.py:137-171) ---------------------------------------------------------------------
   float dx = x, dy = y;
   if (active) {
-    if (a.noise) dx += nx, dy += ny;
-    if (a.miss_u && mu < mp) dx = 0.f, dy = 0.f;
+    if (v.noise) dx += nx, dy += ny;
+    if (v.miss_u && mu < mp) dx = 0.f, dy = 0.f;
   }
   // ---- apply_transform twice: model input (deformed) and target (augmented); shift / scale of the second call ----------
   float ix = dx, iy = dy, ic = conf, tx = x, ty = y, s[2] = {0.f, 0.f}, scale = 1.f;
-  if (a.transform != P2C_TRANSFORM_NONE) {
+  if (v.transform != P2C_TRANSFORM_NONE) {
     float s0[2], sc0, tc;
-    normalise<G>(a, base, active, dx, dy, conf, ix, iy, ic, s0, sc0);
-    normalise<G>(a, base, active, x, y, conf, tx, ty, tc, s, scale);
-    if (a.shift && live && j == 0) a.shift[f * 2] = s[0], a.shift[f * 2 + 1] = s[1];
-    if (a.scale && live && j == 0) a.scale[f] = scale;
+    normalise<G>(v, a.near_zero, base, active, dx, dy, conf, ix, iy, ic, s0, sc0);
+    normalise<G>(v, a.near_zero, base, active, x, y, conf, tx, ty, tc, s, scale);
   }
+  if (a.shift && live && j == 0) a.shift[f * 2] = s[0], a.shift[f * 2 + 1] = s[1];   // hosts refuse these for NONE
+  if (a.scale && live && j == 0) a.scale[f] = scale;
   // ---- node map: lane = model-input joint --------------------------------------------------------------------------------
   const int srcj = (j < a.Ji) ? inv_j : -1;
   const int from = base + (srcj < 0 ? 0 : srcj);
@@ -231,6 +265,56 @@ __global__ __launch_bounds__(256) void collate_kernel(const Args a) {
   if (a.t_projection_2d) st2(a.t_projection_2d + 2 * o, has ? o_x : 0.f, has ? o_y : 0.f);
   if (a.t_deformed) st2(a.t_deformed + 2 * o, has ? o_dx : 0.f, has ? o_dy : 0.f);
   if (a.t_transformed) st2(a.t_transformed + 2 * o, has ? o_tx : 0.f, has ? o_ty : 0.f);
+}
+
+template <int G>
+__global__ __launch_bounds__(256) void collate_kernel(const Args a) {
+  const int lane = threadIdx.x & 63;
+  const int j = lane & (G - 1);
+  const int base = lane & ~(G - 1);
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t f = wave * (64 / G) + (lane / G);           // frame index over N * T
+  const bool live = f < a.frames_total;
+  const int64_t fc = live ? f : 0;
+  const int lj = j & (MAXJ - 1);
+  View v;
+  v.raw = a.raw, v.noise = a.noise, v.miss_u = a.miss_u, v.bboxes = a.bboxes;
+  v.rf = fc, v.Jd = a.Jd, v.Jn = a.Jd, v.C = a.C, v.transform = a.transform, v.n_hips = a.n_hips, v.n_neck = a.n_neck;
+  v.hips_idx[0] = a.hips_idx[0], v.hips_idx[1] = a.hips_idx[1], v.neck_idx[0] = a.neck_idx[0], v.neck_idx[1] = a.neck_idx[1];
+  v.mp = a.miss_prob[lj];                          // per-lane reads of the kernel-argument tables, also up front
+  v.perm_j = a.perm[lj], v.inv_j = a.inv[lj];
+  collate_frame<G>(a, v, j, base, f, fc / a.T, live);
+}
+
+// K26: the same frame, with the source looked up per clip. With G = 32 the two frames of a wave can be of different clips
+// and sources, so everything in View is per lane group (VGPRs); the tables are read from the kernel arguments by lane.
+template <int G>
+__global__ __launch_bounds__(256) void collate_mixed_kernel(const MixedArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int j = lane & (G - 1);
+  const int base = lane & ~(G - 1);
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t f = wave * (64 / G) + (lane / G);
+  const bool live = f < a.frames_total;
+  const int64_t fc = live ? f : 0;
+  const int64_t n = fc / a.T;
+  const int t = (int)(fc - n * a.T);
+  int s = a.source[n];
+  s = s < a.S ? s : a.S - 1;                       // never index past the table, whatever the batch says
+  const Source &q = a.src[s];
+  int64_t r = a.row[n];
+  r = r < 0 ? 0 : (r < q.rows ? r : q.rows - 1);   // nor past the source's clips
+  const int lj = j & (MAXJ - 1);
+  View v;
+  v.raw = q.raw;
+  v.noise = (q.flags & 1) ? a.noise : nullptr, v.miss_u = (q.flags & 2) ? a.miss_u : nullptr;
+  v.bboxes = (q.flags & 4) ? a.bboxes : nullptr;
+  v.rf = r * a.T + t, v.Jd = q.rows > 0 ? q.Jd : 0, v.Jn = a.Jmax, v.C = q.C;    // a source without clips reads nothing
+  v.transform = q.transform, v.n_hips = q.n_hips, v.n_neck = q.n_neck;
+  v.hips_idx[0] = q.hips_idx[0], v.hips_idx[1] = q.hips_idx[1], v.neck_idx[0] = q.neck_idx[0], v.neck_idx[1] = q.neck_idx[1];
+  v.mp = q.miss_prob[lj];
+  v.perm_j = q.perm[lj], v.inv_j = q.inv[lj];
+  collate_frame<G>(a, v, j, base, f, n, live);
 }
 
 }  // namespace p2c_collate
@@ -290,6 +374,75 @@ extern "C" int p2c_collate_fwd(const p2c_collate_desc *d, void *stream_) {
   const dim3 block(256), grid((unsigned)((waves + 3) / 4));
   if (G == 32) hipLaunchKernelGGL(collate_kernel<32>, grid, block, 0, (hipStream_t)stream_, a);
   else hipLaunchKernelGGL(collate_kernel<64>, grid, block, 0, (hipStream_t)stream_, a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+extern "C" int p2c_collate_mixed_fwd(const p2c_collate_mixed_desc *d, void *stream_) {
+  using namespace p2c_collate;
+  if (!d) return P2C_E_NULL;
+  if (d->N == 0) return 0;
+  if (d->S < 1 || d->S > P2C_COLLATE_MAX_SOURCES) return P2C_E_SHAPE;
+  if (!d->source || !d->row || !d->frames) return P2C_E_NULL;
+  if (d->N < 0 || d->T < 1 || d->Ji < 1 || d->Ji > MAXJ) return P2C_E_SHAPE;
+  MixedArgs a{};
+  a.rotation = d->rotation_deg, a.bboxes = d->bboxes, a.clip_size = d->clip_size, a.noise = d->noise, a.miss_u = d->miss_u;
+  a.is_flipped = d->is_flipped, a.source = d->source, a.row = d->row;
+  a.frames = d->frames, a.t_projection_2d = d->t_projection_2d, a.t_deformed = d->t_deformed;
+  a.t_transformed = d->t_transformed, a.shift = d->shift, a.scale = d->scale, a.bboxes_out = d->bboxes_out;
+  a.frames_total = d->N * d->T, a.T = d->T, a.Ji = d->Ji, a.S = d->S, a.near_zero = d->near_zero;
+  a.Cf = d->return_confidence ? 3 : 2;
+  bool wide = d->Ji > 32;
+  for (int s = 0; s < d->S; ++s) {
+    const p2c_collate_source &p = d->sources[s];
+    Source &q = a.src[s];
+    if (p.n < 0 || p.Jd < 1 || p.Jd > MAXJ || (p.C != 2 && p.C != 3)) return P2C_E_SHAPE;
+    if (p.n > 0 && !p.raw) return P2C_E_NULL;
+    if (p.transform < P2C_TRANSFORM_NONE || p.transform > P2C_TRANSFORM_HIPS_NECK_BBOX) return P2C_E_ENUM;
+    if (d->return_confidence && p.C != 3) return P2C_E_SHAPE;
+    if (d->rotation_deg && !p.has_bboxes && p.C != 2) return P2C_E_SHAPE;
+    if (d->is_flipped && !p.flip_perm) return P2C_E_NULL;
+    if (p.has_miss && (!d->miss_u || !p.miss_prob)) return P2C_E_NULL;
+    if (p.has_noise && !d->noise) return P2C_E_NULL;
+    if (p.has_bboxes && !d->bboxes) return P2C_E_NULL;
+    if ((d->t_transformed || d->shift || d->scale) && p.transform == P2C_TRANSFORM_NONE) return P2C_E_ENUM;
+    q.raw = p.raw, q.rows = p.n, q.Jd = p.Jd, q.C = p.C, q.transform = p.transform;
+    q.flags = (p.has_noise ? 1 : 0) | (p.has_miss ? 2 : 0) | (p.has_bboxes ? 4 : 0);
+    if (p.transform != P2C_TRANSFORM_NONE && p.transform != P2C_TRANSFORM_BBOX) {
+      if (p.n_hips < 1 || p.n_hips > 2 || p.n_neck < 1 || p.n_neck > 2) return P2C_E_SHAPE;
+      for (int i = 0; i < p.n_hips; ++i)
+        if (p.hips_idx[i] < 0 || p.hips_idx[i] >= p.Jd) return P2C_E_INDEX;
+      for (int i = 0; i < p.n_neck; ++i)
+        if (p.neck_idx[i] < 0 || p.neck_idx[i] >= p.Jd) return P2C_E_INDEX;
+      q.n_hips = p.n_hips, q.n_neck = p.n_neck;
+      for (int i = 0; i < 2; ++i) q.hips_idx[i] = p.hips_idx[i], q.neck_idx[i] = p.neck_idx[i];
+    }
+    for (int j = 0; j < MAXJ; ++j) q.perm[j] = (int8_t)j, q.inv[j] = -1, q.miss_prob[j] = 0.f;
+    if (p.flip_perm)
+      for (int j = 0; j < p.Jd; ++j) {
+        if (p.flip_perm[j] < 0 || p.flip_perm[j] >= p.Jd) return P2C_E_INDEX;
+        q.perm[j] = (int8_t)p.flip_perm[j];
+      }
+    if (p.miss_prob)
+      for (int j = 0; j < p.Jd; ++j) q.miss_prob[j] = p.miss_prob[j];
+    if (p.K > 0) {
+      if (!p.src_idx || !p.dst_idx) return P2C_E_NULL;
+      for (int k = 0; k < p.K; ++k) {
+        if (p.src_idx[k] < 0 || p.src_idx[k] >= p.Jd || p.dst_idx[k] < 0 || p.dst_idx[k] >= d->Ji) return P2C_E_INDEX;
+        q.inv[p.dst_idx[k]] = (int8_t)p.src_idx[k];
+      }
+    } else {
+      if (d->Ji != p.Jd) return P2C_E_SHAPE;
+      for (int j = 0; j < p.Jd; ++j) q.inv[j] = (int8_t)j;
+    }
+    if (p.Jd > a.Jmax) a.Jmax = p.Jd;
+    wide = wide || p.Jd > 32;
+  }
+  const int G = wide ? 64 : 32;
+  const int64_t waves = (a.frames_total + (64 / G) - 1) / (64 / G);
+  const dim3 block(256), grid((unsigned)((waves + 3) / 4));
+  if (G == 32) hipLaunchKernelGGL(collate_mixed_kernel<32>, grid, block, 0, (hipStream_t)stream_, a);
+  else hipLaunchKernelGGL(collate_mixed_kernel<64>, grid, block, 0, (hipStream_t)stream_, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }

@@ -520,6 +520,150 @@ def collate(raw: Tensor, *, flip_perm: Optional[Sequence[int]] = None, is_flippe
     return frames, targets
 
 
+@dataclass
+class MixedSource:
+    """One source of ``collate_mixed``: its stored clips and what K11 would be told about them."""
+    raw: Tensor                                       # (n,T,Jd,2|3) on the device
+    flip_perm: Optional[Sequence[int]] = None         # flip mask of the data skeleton (needed with is_flipped)
+    miss_prob: Optional[Sequence[float]] = None       # per data joint; clips of this source read miss_u when given
+    transform: str = 'hips_neck_bbox'
+    hips_idx: Sequence[int] = (1,)
+    neck_idx: Sequence[int] = (8,)
+    src_idx: Optional[Sequence[int]] = None           # node map onto the model-input skeleton (None: same skeleton)
+    dst_idx: Optional[Sequence[int]] = None
+    has_noise: bool = False                           # clips of this source add ``noise``
+    has_bboxes: bool = False                          # clips of this source take their boxes from ``bboxes``
+
+
+def check_mixed_index(source, row, counts: Sequence[int]) -> None:
+    """Host-side check of a batch's (source, row) pairs, for the code that builds them (numpy arrays or CPU tensors):
+    the kernel clamps what is out of range instead of following it, which keeps memory safe but hides the mistake."""
+    import numpy as np
+    source, row = np.asarray(source), np.asarray(row)
+    if source.shape != row.shape or source.ndim != 1:
+        raise RuntimeError(f'source and row must be (N,), got {source.shape} and {row.shape}')
+    if source.size == 0:
+        return
+    if source.min() < 0 or source.max() >= len(counts):
+        raise RuntimeError(f'source index outside [0, {len(counts)})')
+    limit = np.asarray(counts, dtype=np.int64)[source]
+    if (row < 0).any() or (row >= limit).any():
+        bad = int(np.flatnonzero((row < 0) | (row >= limit))[0])
+        raise RuntimeError(f'row {int(row[bad])} of batch clip {bad} is outside source {int(source[bad])} '
+                           f'({int(limit[bad])} clips)')
+
+
+def collate_mixed(sources: Sequence[MixedSource], source: Tensor, row: Tensor, *, is_flipped: Optional[Tensor] = None,
+                  rotation: Optional[Tensor] = None, bboxes: Optional[Tensor] = None,
+                  clip_size: Optional[Tensor] = None, noise: Optional[Tensor] = None, miss_u: Optional[Tensor] = None,
+                  near_zero: float = 1e-5, return_confidence: bool = False, n_input_joints: Optional[int] = None
+                  ) -> Tuple[Tensor, Dict[str, Tensor]]:
+    """``collate`` for a batch whose clips come from several data skeletons, in one launch (p2c_collate_mixed_fwd): clip n
+    is ``sources[source[n]].raw[row[n]]`` and is processed exactly as ``collate`` would process it with that source's
+    settings. The draws are indexed by batch position; noise (N,T,Jmax,2) and miss_u (N,T,Jmax) have Jmax = the largest
+    source skeleton. ``source`` (uint8) and ``row`` (int32) are device tensors that the caller has checked where it built
+    them (``check_mixed_index``); the kernel clamps, it does not report. Returns (frames, targets) with ``collate``'s keys;
+    every element of every output is written for every clip."""
+    from pedestrians_video_2_carla_amd._lib import CollateMixedDesc, P2C_COLLATE_MAX_SOURCES
+    lib = _lib.lib()
+    S = len(sources)
+    if not 1 <= S <= P2C_COLLATE_MAX_SOURCES:
+        raise RuntimeError(f'collate_mixed takes 1..{P2C_COLLATE_MAX_SOURCES} sources, got {S}')
+    raws = [_require_device(q.raw, 'projection_2d') for q in sources]
+    device = raws[0].device
+    for r in raws:
+        if r.ndim != 4 or r.shape[-1] not in (2, 3) or r.shape[1] != raws[0].shape[1]:
+            raise RuntimeError(f'every source must be (n,T,J,2|3) with one T, got {[tuple(x.shape) for x in raws]}')
+    T, Jmax = raws[0].shape[1], max(r.shape[2] for r in raws)
+    if return_confidence and any(r.shape[-1] == 2 for r in raws):      # confidence_mixin.py:17-18
+        raise RuntimeError('Tensors must have same number of dimensions: got 3 and 2')
+    if rotation is not None and any(r.shape[-1] != 2 and not q.has_bboxes for r, q in zip(raws, sources)):
+        raise RuntimeError('The size of tensor a (2) must match the size of tensor b (3) at non-singleton dimension 3')
+    if not source.is_cuda or not row.is_cuda:
+        raise _lib.P2CError('source and row must live on the GPU: check them on the host with check_mixed_index first')
+    source = source.to(torch.uint8).contiguous()
+    row = row.to(torch.int32).contiguous()
+    N = source.shape[0]
+    if source.ndim != 1 or tuple(row.shape) != (N,):
+        raise RuntimeError(f'source and row must be (N,), got {tuple(source.shape)} and {tuple(row.shape)}')
+    Ji = n_input_joints if n_input_joints is not None else raws[0].shape[2]
+    f32 = dict(dtype=torch.float32, device=device)
+    d = CollateMixedDesc()
+    d.N, d.T, d.Ji, d.S, d.return_confidence, d.near_zero = N, T, Ji, S, int(return_confidence), near_zero
+    d.source, d.row = source.data_ptr(), row.data_ptr()
+    keep = [raws, source, row]
+
+    def dev(t, shape, name, dtype=torch.float32):
+        t = _require_device(t, name) if dtype == torch.float32 else t.to(device=device, dtype=dtype).contiguous()
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f'{name} must be {shape}, got {tuple(t.shape)}')
+        keep.append(t)
+        return t.data_ptr()
+
+    targets: Dict[str, Tensor] = {}
+    if is_flipped is not None:
+        if any(q.flip_perm is None for q in sources):
+            raise RuntimeError('is_flipped needs the flip mask of every data skeleton')
+        d.is_flipped = dev(is_flipped, (N,), 'is_flipped', torch.uint8)
+        targets['is_flipped'] = is_flipped
+    if rotation is not None:
+        d.rotation_deg = dev(rotation, (N,), 'rotation')
+        targets['rotation'] = rotation
+    augmented = is_flipped is not None or rotation is not None
+    with_boxes = bboxes is not None and augmented
+    if with_boxes:
+        d.bboxes = dev(bboxes, (N, T, 2, 2), 'bboxes')
+        targets['bboxes'] = torch.empty(N, T, 2, 2, **f32)
+        targets['orig_bboxes'] = bboxes
+        d.bboxes_out = targets['bboxes'].data_ptr()
+    if clip_size is not None and augmented:
+        d.clip_size = dev(clip_size, (N, 2), 'clip_size')
+    if noise is not None:
+        d.noise = dev(noise, (N, T, Jmax, 2), 'noise')
+    if miss_u is not None:
+        d.miss_u = dev(miss_u, (N, T, Jmax), 'miss_u')
+    for i, (q, r) in enumerate(zip(sources, raws)):
+        c = d.sources[i]
+        c.n, c.raw, c.Jd, c.C = r.shape[0], r.data_ptr(), r.shape[2], r.shape[3]
+        if q.flip_perm is not None and is_flipped is not None:
+            perm = _iarr(q.flip_perm)
+            c.flip_perm = perm
+            keep.append(perm)
+        if q.miss_prob is not None and miss_u is not None:
+            probs = (ctypes.c_float * r.shape[2])(*[float(v) for v in q.miss_prob])
+            c.miss_prob = probs
+            c.has_miss = 1
+            keep.append(probs)
+        c.transform = TRANSFORM[q.transform]
+        c.n_hips, c.n_neck = len(q.hips_idx), len(q.neck_idx)
+        for k, v in enumerate(q.hips_idx):
+            c.hips_idx[k] = v
+        for k, v in enumerate(q.neck_idx):
+            c.neck_idx[k] = v
+        if q.src_idx is not None:
+            c.K = len(q.src_idx)
+            si, di = _iarr(q.src_idx), _iarr(q.dst_idx)
+            c.src_idx, c.dst_idx = si, di
+            keep.append((si, di))
+        c.has_noise = int(q.has_noise and noise is not None)
+        c.has_bboxes = int(q.has_bboxes and with_boxes)
+    frames = torch.empty(N, T, Ji, 3 if return_confidence else 2, **f32)
+    targets['projection_2d'] = torch.empty(N, T, Ji, 2, **f32)
+    d.frames, d.t_projection_2d = frames.data_ptr(), targets['projection_2d'].data_ptr()
+    if noise is not None or miss_u is not None:
+        targets['projection_2d_deformed'] = torch.empty(N, T, Ji, 2, **f32)
+        d.t_deformed = targets['projection_2d_deformed'].data_ptr()
+    if any(q.transform != 'none' for q in sources):       # the library refuses a mix of 'none' and a transform
+        targets['projection_2d_transformed'] = torch.empty(N, T, Ji, 2, **f32)
+        targets['projection_2d_shift'] = torch.empty(N, T, 2, **f32)
+        targets['projection_2d_scale'] = torch.empty(N, T, **f32)
+        d.t_transformed, d.shift = targets['projection_2d_transformed'].data_ptr(), targets['projection_2d_shift'].data_ptr()
+        d.scale = targets['projection_2d_scale'].data_ptr()
+    with torch.cuda.device(device):
+        _lib.check(lib.p2c_collate_mixed_fwd(ctypes.byref(d), _stream()), 'p2c_collate_mixed_fwd')
+    return frames, targets
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # fused small MLP (LinearAE) on fp32 MFMA
 # ----------------------------------------------------------------------------------------------------------------------
