@@ -1208,9 +1208,11 @@ class LSTMRecurrenceFunction(torch.autograd.Function):
         if not zero:
             g_h0, g_c0 = torch.empty(B, H, **f32), torch.empty(B, H, **f32)
             d.c0, d.g_h0, d.g_c0 = c0.data_ptr(), g_h0.data_ptr(), g_c0.data_ptr()
-        d.g_out = _ptr(None if g_out is None else _require_device(g_out, 'grad out'))
-        d.g_hT = _ptr(None if g_hT is None else _require_device(g_hT, 'grad hT'))
-        d.g_cT = _ptr(None if g_cT is None else _require_device(g_cT, 'grad cT'))
+        # (locals: a strided gradient is copied, and the copy has to outlive the launch that reads it)
+        g_out = None if g_out is None else _require_device(g_out, 'grad out')
+        g_hT = None if g_hT is None else _require_device(g_hT, 'grad hT')
+        g_cT = None if g_cT is None else _require_device(g_cT, 'grad cT')
+        d.g_out, d.g_hT, d.g_cT = _ptr(g_out), _ptr(g_hT), _ptr(g_cT)
         d.g_gx = g_gx.data_ptr()
         with torch.cuda.device(out.device):
             if ctx.steps:
@@ -1321,8 +1323,9 @@ class GRURecurrenceFunction(torch.autograd.Function):
         if not zero:
             g_h0 = torch.empty(B, H, **f32)
             d.h0, d.g_h0 = h0.data_ptr(), g_h0.data_ptr()
-        d.g_out = _ptr(None if g_out is None else _require_device(g_out, 'grad out'))
-        d.g_hT = _ptr(None if g_hT is None else _require_device(g_hT, 'grad hT'))
+        g_out = None if g_out is None else _require_device(g_out, 'grad out')      # (locals: the copies outlive the launch)
+        g_hT = None if g_hT is None else _require_device(g_hT, 'grad hT')
+        d.g_out, d.g_hT = _ptr(g_out), _ptr(g_hT)
         d.g_gx, d.g_gh = g_gx.data_ptr(), g_gh.data_ptr()
         with torch.cuda.device(out.device):
             ws = torch.empty(lib.p2c_gru_steps_workspace_floats(B, H), **f32)
@@ -1613,6 +1616,7 @@ def atb(a: Tensor, b: Tensor, bias: bool = False, out: Optional[Tensor] = None, 
     K, M, N = a.shape[0], a.shape[1], b.shape[1]
     if b.shape[0] != K:
         raise RuntimeError('atb: row counts differ')
+    a_scale = None if a_scale is None else _require_device(a_scale, 'a_scale')       # the kernel reads it with unit stride
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=a.device)
     flags = (1 if accumulate else 0) | (2 if (accumulate and bias_out is not None) else 0)   # a fresh bias vector is overwritten
@@ -1724,7 +1728,8 @@ def gemm(a: Tensor, b: Tensor, trans_b: bool, bias: Optional[Tensor] = None, act
     d.ldaux = (aux if aux is not None else aux_out).stride(0) if (aux is not None or aux_out is not None) else 0
     if row_scale is not None and row_scale.numel() * rows_per_scale < M:
         raise RuntimeError('gemm: row_scale is too short')
-    d.row_scale = _ptr(None if row_scale is None else _require_device(row_scale, 'row_scale'))
+    row_scale = None if row_scale is None else _require_device(row_scale, 'row_scale')       # (a local: a copy outlives the launch)
+    d.row_scale = _ptr(row_scale)
     if residual is not None and (tuple(residual.shape) != (M, N) or residual.stride(1) != 1):
         raise RuntimeError(f'gemm: residual should be ({M}, {N}) with unit inner stride')
     d.residual, d.ldr = _ptr(residual), (residual.stride(0) if residual is not None else 0)
@@ -1744,6 +1749,7 @@ def gemm_tn(a: Tensor, b: Tensor, out: Optional[Tensor] = None, accumulate: bool
     if a.ndim != 2 or b.ndim != 2 or a.stride(1) != 1 or b.stride(1) != 1 or a.shape[0] != b.shape[0]:
         raise RuntimeError('gemm_tn: (K, M) and (K, N) operands with unit inner stride expected')
     K, M, N = a.shape[0], a.shape[1], b.shape[1]
+    a_scale = None if a_scale is None else _require_device(a_scale, 'a_scale')       # the kernel reads it with unit stride
     if out is None:
         out, accumulate = torch.empty(M, N, dtype=torch.float32, device=a.device), False
     _check_out(out, (M, N), a.device, 'gemm_tn: out')
@@ -2205,7 +2211,7 @@ def small_attention_supported(N: int, heads: int, head_dim: int) -> bool:
 
 
 def _aligned16(t: Tensor) -> Tensor:
-    """K14 moves 16 bytes at a time and refuses other pointers: a dense view that starts inside a larger buffer (``buf[1:]``
+    """K14 and K15 move 16 bytes at a time and refuse other pointers: a dense view that starts inside a larger buffer (``buf[1:]``
     passes ``contiguous()`` unchanged) is copied into an allocation of its own."""
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
@@ -2259,7 +2265,7 @@ class LayerNormFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps: float):
         lib = _lib.lib()
-        x, weight, bias = _require_device(x, 'x'), _require_device(weight, 'weight'), _require_device(bias, 'bias')
+        x, weight, bias = _aligned16(_require_device(x, 'x')), _require_device(weight, 'weight'), _require_device(bias, 'bias')
         D = x.shape[-1]
         rows = x.numel() // D
         y = torch.empty_like(x)
@@ -2276,7 +2282,7 @@ class LayerNormFunction(torch.autograd.Function):
         x, weight, bias, stats = ctx.saved_tensors
         D = x.shape[-1]
         rows = x.numel() // D
-        gy = _require_device(gy, 'grad')
+        gy = _aligned16(_require_device(gy, 'grad'))
         gx = torch.empty_like(x)
         sw, sb = _sink(weight), _sink(bias)
         if sw is None or sb is None:
@@ -2461,8 +2467,9 @@ class FrameMeanFunction(torch.autograd.Function):
         B, F, C = x.shape
         if C % 4 == 0 and x.data_ptr() % 16 == 0:
             out = torch.empty(B, C, dtype=torch.float32, device=x.device)
+            wc, bc = w.contiguous(), b.contiguous()                          # (locals: a copy outlives the launch)
             with torch.cuda.device(x.device):
-                _lib.check(_lib.lib().p2c_frame_mean_fwd(x.data_ptr(), w.contiguous().data_ptr(), b.contiguous().data_ptr(),
+                _lib.check(_lib.lib().p2c_frame_mean_fwd(x.data_ptr(), wc.data_ptr(), bc.data_ptr(),
                                                          out.data_ptr(), B, F, C, _stream()), 'p2c_frame_mean_fwd')
             return out
         return (x * w.view(1, -1, 1)).sum(1) + b.view(1, 1)
@@ -2542,7 +2549,7 @@ class TransformerBlockFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, f1, f2, heads, scale, eps1, eps2, n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2):
-        x = _require_device(x, 'x').contiguous()
+        x = _aligned16(_require_device(x, 'x'))
         S, N, C = x.shape
         rows = S * N
         x2 = x.view(rows, C)
@@ -2567,7 +2574,7 @@ class TransformerBlockFunction(torch.autograd.Function):
         x2, h1, st1, qkv, att, x1, h2, st2, z, a, f1, f2 = ctx.saved_tensors
         n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2 = ctx.params
         S, N, C, heads, scale = ctx.geom
-        g = _require_device(g, 'grad').contiguous().view(S * N, C)
+        g = _aligned16(_require_device(g, 'grad')).view(S * N, C)
         with torch.cuda.device(g.device):
             dz = gemm(g, w2, False, act=2, aux=z, row_scale=f2, rows_per_scale=N)
             gw2, gb2 = weight_grad(g, a, w2, b2, f2, N)
@@ -2894,9 +2901,9 @@ class DenseChainFunction(torch.autograd.Function):
         hs, relus = ctx.saved_tensors, ctx.relus
         n = len(relus)
         weights, biases = ctx.params[:n], ctx.params[n:]
-        g = _require_device(gy, 'grad')
+        g = gy = _require_device(gy, 'grad')     # (gy keeps a copy alive to the end: no launch below may find one of its operands freed)
         if relus[-1]:                                # no GEMM behind the last layer whose epilogue could carry its mask
-            g = torch.ops.aten.threshold_backward(g, hs[-1], 0.0)
+            g = torch.ops.aten.threshold_backward(gy, hs[-1], 0.0)
         gws, gbs, gx = [None] * n, [None] * n, None
         for l in range(n - 1, -1, -1):
             gws[l], gbs[l] = weight_grad(g, hs[l], weights[l], biases[l])
