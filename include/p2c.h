@@ -851,6 +851,35 @@ P2C_API int64_t p2c_relu_stack_workspace_floats(const p2c_relu_stack_desc *desc)
 P2C_API int p2c_relu_stack_fwd(const p2c_relu_stack_desc *desc, void *stream);
 P2C_API int p2c_relu_stack_bwd(const p2c_relu_stack_desc *desc, void *stream);
 
+/* ---- pose_changes / cum_pose_changes losses (K27, csrc/p2c_pose_change_loss.hip) -------------------------------------------------
+ * nn.MSELoss between predicted and target pose changes (reference loss/pose_changes.py:7-28, cumulative = 0: M_t against G_t) or
+ * between their running products over the frames (loss/cum_pose_changes.py:9-56, cumulative = 1: C_t = C_{t-1} M_t with
+ * C_{-1} = I against the same left-to-right product of the targets), per (clip, joint), in fp32.
+ *   pred     (B,T,J,6) raw 6-D rotations (pred_is_6d = 1: orthonormalised in-kernel by the pose head's rot6d_fwd, 8-byte aligned)
+ *            or (B,T,J,3,3) matrices (pred_is_6d = 0; they need not be orthonormal);   target (B,T,J,3,3).
+ *   mean     1: loss = sum / (B T J 9) -- 9 for 6-D input too, the comparison is over matrices; 0: reduction='sum'.
+ *   max_blocks  0: the kernel's own grid cap; > 0 lowers it (a test reaches the grid-stride regime with a handful of chains).
+ * _fwd (one launch behind a 16-byte memset node): *loss, and in `workspace` (p2c_pose_change_loss_workspace_floats floats,
+ *   16-byte aligned, nothing in it is read before the call has written it) the differences and running products _bwd reads.
+ * _bwd (one launch; same desc, the workspace as _fwd left it): grad_pred (layout of pred) = d loss / d pred times *grad_loss
+ *   (a device float). No gradient is formed for the target. The running product C_{t-1} is read back, never obtained by
+ *   inverting a step.
+ * No masking: a NaN anywhere gives a NaN loss. The reduction has a fixed order and uses no float atomics: loss and gradient are
+ * bit-identical from run to run. Any T >= 1, J >= 1, B >= 0 (B = 0: nothing is launched, nothing written). Element indices are
+ * 32-bit: B T J 9 >= 2^31 is refused (P2C_E_SHAPE). Flags outside {0, 1}: P2C_E_ENUM. Every refusal comes before any launch. */
+typedef struct p2c_pose_change_loss_desc {
+  int64_t B;
+  int32_t T, J;
+  int32_t pred_is_6d, cumulative, mean, max_blocks;
+  const float *pred, *target;
+  float *workspace, *loss;
+  const float *grad_loss;
+  float *grad_pred;
+} p2c_pose_change_loss_desc;
+P2C_API int64_t p2c_pose_change_loss_workspace_floats(const p2c_pose_change_loss_desc *desc);
+P2C_API int p2c_pose_change_loss_fwd(const p2c_pose_change_loss_desc *desc, void *stream);
+P2C_API int p2c_pose_change_loss_bwd(const p2c_pose_change_loss_desc *desc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

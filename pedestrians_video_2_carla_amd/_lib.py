@@ -172,6 +172,13 @@ class ReluStackDesc(ctypes.Structure):
                 ('accumulate', _i32), ('workspace', _f32p)]
 
 
+class PoseChangeLossDesc(ctypes.Structure):
+    """p2c_pose_change_loss_desc (include/p2c.h)."""
+    _fields_ = [('B', _i64), ('T', _i32), ('J', _i32), ('pred_is_6d', _i32), ('cumulative', _i32), ('mean', _i32),
+                ('max_blocks', _i32), ('pred', _f32p), ('target', _f32p), ('workspace', _f32p), ('loss', _f32p),
+                ('grad_loss', _f32p), ('grad_pred', _f32p)]
+
+
 SYMBOLS = {
     'p2c_version': (ctypes.c_char_p, []),
     'p2c_pose_head_workspace_floats': (_i64, [_i32]),
@@ -270,6 +277,9 @@ SYMBOLS = {
     'p2c_relu_stack_workspace_floats': (_i64, [ctypes.POINTER(ReluStackDesc)]),
     'p2c_relu_stack_fwd': (ctypes.c_int, [ctypes.POINTER(ReluStackDesc), _vp]),
     'p2c_relu_stack_bwd': (ctypes.c_int, [ctypes.POINTER(ReluStackDesc), _vp]),
+    'p2c_pose_change_loss_workspace_floats': (_i64, [ctypes.POINTER(PoseChangeLossDesc)]),
+    'p2c_pose_change_loss_fwd': (ctypes.c_int, [ctypes.POINTER(PoseChangeLossDesc), _vp]),
+    'p2c_pose_change_loss_bwd': (ctypes.c_int, [ctypes.POINTER(PoseChangeLossDesc), _vp]),
 }
 
 _lib = None

@@ -2922,3 +2922,86 @@ def dense_chain(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Tensor], 
         raise RuntimeError('dense_chain: 2-D x and one weight, bias and ReLU flag per layer expected')
     return DenseChainFunction.apply(x, tuple(relus), *[_require_device(w, 'weight') for w in weights],
                                     *[_require_device(b, 'bias') for b in biases])
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# pose_changes / cum_pose_changes losses (K27, csrc/p2c_pose_change_loss.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def pcl_framework() -> bool:
+    """P2C_PCL_FRAMEWORK=1: the two pose-change losses run as tensor ops on the device (the comparison arm of
+    tools/bench_pose_change_loss.py)."""
+    return os.environ.get('P2C_PCL_FRAMEWORK', '0') == '1'
+
+
+def _pcl_layout_ok(pred: Tensor, target: Tensor) -> bool:
+    if target.ndim != 5 or tuple(target.shape[-2:]) != (3, 3):
+        return False
+    if pred.ndim == 4 and pred.shape[-1] == 6:
+        return pred.shape[:3] == target.shape[:3]
+    return pred.ndim == 5 and pred.shape == target.shape
+
+
+def pose_change_loss_supported(pred: Tensor, target: Tensor, criterion) -> bool:
+    """What K27 covers: fp32 device tensors, ``pred`` (B,T,J,6) or (B,T,J,3,3) against ``target`` (B,T,J,3,3), ``nn.MSELoss``
+    with reduction 'mean' or 'sum', at least one element and fewer than 2^31 (the kernel indexes with 32 bits). Everything
+    else -- host tensors, fp64, other criteria -- and ``P2C_PCL_FRAMEWORK=1`` is the losses' tensor code."""
+    return (type(criterion) is torch.nn.MSELoss and criterion.reduction in ('mean', 'sum')
+            and isinstance(pred, Tensor) and isinstance(target, Tensor)
+            and pred.is_cuda and target.is_cuda and pred.device == target.device
+            and pred.dtype == torch.float32 and target.dtype == torch.float32 and _pcl_layout_ok(pred, target)
+            and 0 < target.numel() < 2 ** 31 and not pcl_framework() and not torch.is_autocast_enabled())
+
+
+def _pcl_desc(pred: Tensor, target: Tensor, cumulative: bool, mean: bool, max_blocks: int = 0):
+    d = _lib.PoseChangeLossDesc()
+    d.B, d.T, d.J = target.shape[0], target.shape[1], target.shape[2]
+    d.pred_is_6d, d.cumulative, d.mean, d.max_blocks = int(pred.ndim == 4), int(bool(cumulative)), int(bool(mean)), int(max_blocks)
+    d.pred, d.target = pred.data_ptr(), target.data_ptr()
+    return d
+
+
+class PoseChangeLossFunction(torch.autograd.Function):
+    """loss = K27(pred, target): one launch forward, one backward. The forward leaves the differences and the running products
+    in a workspace the backward reads; the gradient goes to the prediction only."""
+
+    @staticmethod
+    def forward(ctx, pred, target, cumulative: bool, mean: bool, max_blocks: int):
+        lib = _lib.lib()
+        pred, target = _aligned16(_require_device(pred, 'pose changes')), _require_device(target, 'target pose changes')
+        if not _pcl_layout_ok(pred, target):
+            raise RuntimeError(f'pose_change_loss: prediction {tuple(pred.shape)} against target {tuple(target.shape)}; '
+                               '(B,T,J,6) or (B,T,J,3,3) against (B,T,J,3,3) expected')
+        desc = _pcl_desc(pred, target, cumulative, mean, max_blocks)
+        n_ws = lib.p2c_pose_change_loss_workspace_floats(ctypes.byref(desc))
+        _lib.check(min(n_ws, 0), 'p2c_pose_change_loss_workspace_floats')
+        f32 = dict(dtype=torch.float32, device=pred.device)
+        ws, loss = torch.empty(n_ws, **f32), torch.zeros(1, **f32)
+        desc.workspace, desc.loss = ws.data_ptr(), loss.data_ptr()
+        with torch.cuda.device(pred.device):
+            _lib.check(lib.p2c_pose_change_loss_fwd(ctypes.byref(desc), _stream()), 'p2c_pose_change_loss_fwd')
+        ctx.save_for_backward(pred, target, ws)
+        ctx.cfg = (bool(cumulative), bool(mean), int(max_blocks))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        lib = _lib.lib()
+        pred, target, ws = ctx.saved_tensors
+        g_loss = _require_device(g_loss, 'grad').reshape(1)       # (a local: an expanded scalar is copied, the copy outlives the launch)
+        gp = torch.empty_like(pred)
+        desc = _pcl_desc(pred, target, *ctx.cfg)
+        desc.workspace, desc.grad_loss, desc.grad_pred = ws.data_ptr(), g_loss.data_ptr(), gp.data_ptr()
+        with torch.cuda.device(pred.device):
+            _lib.check(lib.p2c_pose_change_loss_bwd(ctypes.byref(desc), _stream()), 'p2c_pose_change_loss_bwd')
+        return gp, None, None, None, None
+
+
+def pose_change_loss(pred: Tensor, target: Tensor, cumulative: bool, reduction: str = 'mean', max_blocks: int = 0) -> Tensor:
+    """K27: ``MSELoss(reduction)`` between the pose changes ``pred`` -- (B,T,J,6) raw 6-D rotations or (B,T,J,3,3) matrices -- and
+    ``target`` (B,T,J,3,3) directly (``cumulative=False``, the reference's pose_changes) or between their running products
+    over the frames (``cumulative=True``, cum_pose_changes). The mean divides by B T J 9 for either layout. fp32 device
+    tensors; views are copied (``pose_change_loss_supported`` says what is covered: there is no framework fallback here).
+    ``max_blocks`` lowers the kernel's grid cap (tests)."""
+    if reduction not in ('mean', 'sum'):
+        raise RuntimeError(f"pose_change_loss: reduction '{reduction}' (mean or sum expected)")
+    return PoseChangeLossFunction.apply(pred, target, bool(cumulative), reduction == 'mean', int(max_blocks))
