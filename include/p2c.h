@@ -880,6 +880,63 @@ P2C_API int64_t p2c_pose_change_loss_workspace_floats(const p2c_pose_change_loss
 P2C_API int p2c_pose_change_loss_fwd(const p2c_pose_change_loss_desc *desc, void *stream);
 P2C_API int p2c_pose_change_loss_bwd(const p2c_pose_change_loss_desc *desc, void *stream);
 
+/* ---- heatmap head of the pose-estimation flow (K28, csrc/p2c_heatmaps.hip) ----------------------------------------------------
+ * All fp32, dense row-major tensors, fixed-order reductions, no float atomics: two runs give the same bits.
+ *
+ * p2c_heatmap_targets_fwd (K28a, one launch): the target maps of N = B T frames, reference VideoMixin._get_heatmap +
+ * gaussian_kernel + the flow's avg_pool2d(k, s, p) (count_include_pad), written pooled; the full-resolution maps are not formed.
+ *   kp (N,J,2) pixel keypoints, shift (N,2); centre = rint((kp - shift) * (scale_x, scale_y)) in fp32, round-half-even; a
+ *   non-finite or |centre| >= 2^30 one has no support.   table[d2], n_table <= 1024 entries: the Gaussian of the integer squared
+ *   distance, clamps applied, built by the caller; d2 >= n_table reads as 0.   out (N,J+1,oh,ow): channel 0 = 1 - max_j,
+ *   channel j + 1 = joint j; oh = (H + 2p - k) / s + 1 (ow alike) must be what the caller states.   k = 1, s = 1, p = 0 is full
+ *   resolution, bit for bit the table's values.   1 <= J <= 63, 1 <= k <= 32, 2p <= k. A cell whose window meets no support is 0.0f.
+ * p2c_heatmaps_loss_fwd (K28b, two launches) / _bwd (one): BasePoseLoss's sum_per_frame with nn.MSELoss('mean') over maps.
+ *   pred (B,T,Pp,h,w), gt (B,T,Pg,h,w); pair k < K <= 64 compares pred channel pred_channels[k] with gt channel gt_channels[k].
+ *   Pair k is selected in (b,t) when mask = 0, or k == forced (-1: none), or every cell of its gt map is != 0.
+ *   loss = sum_t S_t / (n_t h w) over the frames with n_t > 0 selected pairs and a non-NaN sum S_t; no such frame: 0.
+ *   _fwd writes partials (B,T,K) floats, flags (B,T,K) int32 (the selection), coef (T) floats and *loss; _bwd reads flags and coef
+ *   as _fwd left them and writes grad_pred (layout of pred, every element: 0 for unlisted channels and skipped frames) =
+ *   d loss / d pred times *grad_loss (a device float). B = 0: loss 0.
+ * p2c_heatmap_keypoints_fwd (K28c, one launch): reference _keypoints_from_heatmaps. maps (N,P,h,w), 2 <= P <= 64; out (N,P-1,3) =
+ *   (col * sw, row * sh, c) of the maximum c of map p + 1 at its first flat index if c > 0 and the map holds no NaN, else zeros.
+ * P2C_E_SHAPE / P2C_E_ENUM / P2C_E_NULL before any launch. */
+#define P2C_HEATMAPS_MAX_MAPS 64
+#define P2C_HEATMAPS_MAX_TABLE 1024
+#define P2C_HEATMAPS_MAX_POOL 32
+typedef struct p2c_heatmap_targets_desc {
+  int64_t N;
+  int32_t J, H, W;
+  int32_t k, s, p;
+  int32_t oh, ow;
+  int32_t n_table;
+  float scale_x, scale_y;
+  const float *kp, *shift, *table;
+  float *out;
+} p2c_heatmap_targets_desc;
+typedef struct p2c_heatmaps_loss_desc {
+  int64_t B;
+  int32_t T, Pp, Pg, h, w;
+  int32_t K, forced, mask;
+  int32_t pred_channels[P2C_HEATMAPS_MAX_MAPS], gt_channels[P2C_HEATMAPS_MAX_MAPS];
+  const float *pred, *gt;
+  float *partials;
+  int32_t *flags;
+  float *coef, *loss;
+  const float *grad_loss;
+  float *grad_pred;
+} p2c_heatmaps_loss_desc;
+typedef struct p2c_heatmap_keypoints_desc {
+  int64_t N;
+  int32_t P, h, w;
+  float sw, sh;
+  const float *maps;
+  float *out;
+} p2c_heatmap_keypoints_desc;
+P2C_API int p2c_heatmap_targets_fwd(const p2c_heatmap_targets_desc *desc, void *stream);
+P2C_API int p2c_heatmaps_loss_fwd(const p2c_heatmaps_loss_desc *desc, void *stream);
+P2C_API int p2c_heatmaps_loss_bwd(const p2c_heatmaps_loss_desc *desc, void *stream);
+P2C_API int p2c_heatmap_keypoints_fwd(const p2c_heatmap_keypoints_desc *desc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,30 @@ class PoseChangeLossDesc(ctypes.Structure):
                 ('grad_loss', _f32p), ('grad_pred', _f32p)]
 
 
+class HeatmapTargetsDesc(ctypes.Structure):
+    """p2c_heatmap_targets_desc (include/p2c.h)."""
+    _fields_ = [('N', _i64), ('J', _i32), ('H', _i32), ('W', _i32), ('k', _i32), ('s', _i32), ('p', _i32), ('oh', _i32),
+                ('ow', _i32), ('n_table', _i32), ('scale_x', ctypes.c_float), ('scale_y', ctypes.c_float), ('kp', _f32p),
+                ('shift', _f32p), ('table', _f32p), ('out', _f32p)]
+
+
+HEATMAPS_MAX_MAPS, HEATMAPS_MAX_TABLE, HEATMAPS_MAX_POOL = 64, 1024, 32
+
+
+class HeatmapsLossDesc(ctypes.Structure):
+    """p2c_heatmaps_loss_desc (include/p2c.h)."""
+    _fields_ = [('B', _i64), ('T', _i32), ('Pp', _i32), ('Pg', _i32), ('h', _i32), ('w', _i32), ('K', _i32), ('forced', _i32),
+                ('mask', _i32), ('pred_channels', _i32 * HEATMAPS_MAX_MAPS), ('gt_channels', _i32 * HEATMAPS_MAX_MAPS),
+                ('pred', _f32p), ('gt', _f32p), ('partials', _f32p), ('flags', _vp), ('coef', _f32p), ('loss', _f32p),
+                ('grad_loss', _f32p), ('grad_pred', _f32p)]
+
+
+class HeatmapKeypointsDesc(ctypes.Structure):
+    """p2c_heatmap_keypoints_desc (include/p2c.h)."""
+    _fields_ = [('N', _i64), ('P', _i32), ('h', _i32), ('w', _i32), ('sw', ctypes.c_float), ('sh', ctypes.c_float),
+                ('maps', _f32p), ('out', _f32p)]
+
+
 SYMBOLS = {
     'p2c_version': (ctypes.c_char_p, []),
     'p2c_pose_head_workspace_floats': (_i64, [_i32]),
@@ -280,6 +304,10 @@ SYMBOLS = {
     'p2c_pose_change_loss_workspace_floats': (_i64, [ctypes.POINTER(PoseChangeLossDesc)]),
     'p2c_pose_change_loss_fwd': (ctypes.c_int, [ctypes.POINTER(PoseChangeLossDesc), _vp]),
     'p2c_pose_change_loss_bwd': (ctypes.c_int, [ctypes.POINTER(PoseChangeLossDesc), _vp]),
+    'p2c_heatmap_targets_fwd': (ctypes.c_int, [ctypes.POINTER(HeatmapTargetsDesc), _vp]),
+    'p2c_heatmaps_loss_fwd': (ctypes.c_int, [ctypes.POINTER(HeatmapsLossDesc), _vp]),
+    'p2c_heatmaps_loss_bwd': (ctypes.c_int, [ctypes.POINTER(HeatmapsLossDesc), _vp]),
+    'p2c_heatmap_keypoints_fwd': (ctypes.c_int, [ctypes.POINTER(HeatmapKeypointsDesc), _vp]),
 }
 
 _lib = None

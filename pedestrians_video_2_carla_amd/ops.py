@@ -3005,3 +3005,260 @@ def pose_change_loss(pred: Tensor, target: Tensor, cumulative: bool, reduction: 
     if reduction not in ('mean', 'sum'):
         raise RuntimeError(f"pose_change_loss: reduction '{reduction}' (mean or sum expected)")
     return PoseChangeLossFunction.apply(pred, target, bool(cumulative), reduction == 'mean', int(max_blocks))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# heatmap head of the pose-estimation flow (K28, csrc/p2c_heatmaps.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+HEATMAPS_POOL = (9, 8, 1)            # the flow's target resize: avg_pool2d(kernel 9, stride 8, padding 1)
+_HM_FAR = 2 ** 30                    # a centre no window reaches: where non-finite or huge keypoints land (kernel: kFar)
+
+
+def heatmaps_framework() -> bool:
+    """P2C_HEATMAPS_FRAMEWORK=1: the three heatmap ops run their tensor restatements on the device (the comparison arm of
+    tools/bench_heatmaps.py)."""
+    return os.environ.get('P2C_HEATMAPS_FRAMEWORK', '0') == '1'
+
+
+def _hm_kernel_ok(*tensors: Tensor) -> bool:
+    return (all(isinstance(t, Tensor) and t.is_cuda and t.dtype == torch.float32 and t.device == tensors[0].device for t in tensors)
+            and not heatmaps_framework() and not torch.is_autocast_enabled())
+
+
+_gaussian_tables: Dict[tuple, Tensor] = {}
+
+
+def gaussian_table(sigma, device=None) -> Tensor:
+    """g[d2] = float32(exp(-d2 / 2 / sigma / sigma)) for the integer squared distances d2 = 0, 1, ..., formed in fp64 with both
+    clamps of the reference's gaussian_kernel (> 1 -> 1, < 0.0099 -> 0) before the cast, up to and including the first zero
+    (11 entries for sigma = 1, 85 for sigma = 3); every later entry is zero. Cached per (sigma, device)."""
+    import numpy as np
+    key = (float(sigma), str(device))
+    if key not in _gaussian_tables:
+        if not sigma > 0:
+            raise ValueError(f'gaussian_table: sigma {sigma}')
+        n = int(-2.0 * float(sigma) ** 2 * np.log(0.0099)) + 3          # past the cut, whatever the rounding
+        g = np.exp(-np.arange(n) / 2.0 / sigma / sigma)
+        g[g > 1] = 1
+        g[g < 0.0099] = 0
+        first_zero = int(np.argmin(g > 0))
+        assert g[first_zero] == 0 and first_zero > 0
+        _gaussian_tables[key] = torch.from_numpy(g[:first_zero + 1]).float().to(device or 'cpu')
+    return _gaussian_tables[key]
+
+
+def _pool_out(size: int, k: int, s: int, p: int) -> int:
+    return (size + 2 * p - k) // s + 1
+
+
+def heatmap_centres(projection_2d: Tensor, shift: Tensor, scale) -> Tensor:
+    """``((kp - shift) * scale).round()`` in the keypoints' own precision, as int64; non-finite and huge values go to a far
+    corner whose Gaussian reaches no frame (the reference's ``.int()`` is undefined there)."""
+    scale = torch.as_tensor(scale, dtype=torch.float32).to(device=projection_2d.device, dtype=projection_2d.dtype)
+    c = ((projection_2d - shift.to(projection_2d.dtype)[..., None, :]) * scale).round()
+    c = torch.where((c > -_HM_FAR) & (c < _HM_FAR), c, torch.full_like(c, -_HM_FAR))
+    return c.long()
+
+
+def _heatmap_targets_tensor(projection_2d: Tensor, shift: Tensor, scale, size, sigma, pool) -> Tensor:
+    H, W = int(size[0]), int(size[1])
+    dev = projection_2d.device
+    table = gaussian_table(sigma, dev)
+    n = table.numel()
+    table = torch.cat((table, table.new_zeros(1))).to(projection_2d.dtype)
+    c = heatmap_centres(projection_2d[..., :2], shift, scale)                            # (B,T,J,2)
+    dx = torch.arange(W, device=dev) - c[..., 0, None]                                    # (B,T,J,W)
+    dy = torch.arange(H, device=dev) - c[..., 1, None]
+    d2 = (dy * dy)[..., :, None] + (dx * dx)[..., None, :]                                # (B,T,J,H,W)
+    g = table[d2.clamp_(max=n)]
+    out = torch.cat((1 - g.max(dim=2, keepdim=True).values, g), dim=2)
+    if pool is not None:
+        k, s, p = pool
+        out = torch.nn.functional.avg_pool2d(out.flatten(0, 1), kernel_size=k, stride=s, padding=p).unflatten(0, out.shape[:2])
+    return out
+
+
+def heatmap_targets_supported(projection_2d: Tensor, shift: Tensor, sigma, pool) -> bool:
+    """What K28a covers: fp32 device keypoints outside autocast, at most 63 joints (64 maps), a Gaussian table of at most 1 024
+    entries and a pooling window of at most 32; everything else, and ``P2C_HEATMAPS_FRAMEWORK=1``, is the tensor path."""
+    k, s, p = pool if pool is not None else (1, 1, 0)
+    return (_hm_kernel_ok(projection_2d, shift) and projection_2d.ndim == 4 and 1 <= projection_2d.shape[2] < _lib.HEATMAPS_MAX_MAPS
+            and gaussian_table(sigma).numel() <= _lib.HEATMAPS_MAX_TABLE and 1 <= k <= _lib.HEATMAPS_MAX_POOL and 2 * p <= k)
+
+
+def heatmap_targets(projection_2d: Tensor, shift: Tensor, scale, size, sigma=1, pool=HEATMAPS_POOL) -> Tensor:
+    """Target maps (B,T,J+1,oh,ow) of the pose-estimation flow straight from the keypoints: the reference's ``_get_heatmap``
+    (Gaussians of ``sigma`` around ``rint((kp - shift) * scale)`` on a ``size`` = (H, W) frame, background first) and the flow's
+    ``avg_pool2d(*pool)`` in one launch (K28a); ``pool=None`` gives the full-resolution maps, bit for bit the reference's.
+    ``projection_2d`` (B,T,J,>=2) pixels, ``shift`` (B,T,2), ``scale`` = (clip_w / original_w, clip_h / original_h)."""
+    if projection_2d.ndim != 4 or projection_2d.shape[-1] < 2 or tuple(shift.shape) != (*projection_2d.shape[:2], 2):
+        raise RuntimeError(f'heatmap_targets: keypoints {tuple(projection_2d.shape)} with shifts {tuple(shift.shape)}; '
+                           '(B,T,J,>=2) with (B,T,2) expected')
+    if pool is not None:
+        pool = tuple(int(v) for v in pool)
+    if not heatmap_targets_supported(projection_2d, shift, sigma, pool):
+        return _heatmap_targets_tensor(projection_2d, shift, scale, size, sigma, pool)
+    lib = _lib.lib()
+    kp, shift = projection_2d[..., :2].contiguous(), shift.contiguous()
+    table = gaussian_table(sigma, kp.device)
+    B, T, Jn = kp.shape[:3]
+    k, s, p = pool if pool is not None else (1, 1, 0)
+    sx, sy = (float(v) for v in torch.as_tensor(scale, dtype=torch.float32).reshape(2))
+    d = _lib.HeatmapTargetsDesc()
+    d.N, d.J, d.H, d.W, d.k, d.s, d.p = B * T, Jn, int(size[0]), int(size[1]), k, s, p
+    d.oh, d.ow, d.n_table, d.scale_x, d.scale_y = _pool_out(d.H, k, s, p), _pool_out(d.W, k, s, p), table.numel(), sx, sy
+    out = torch.empty(B, T, Jn + 1, max(d.oh, 0), max(d.ow, 0), dtype=torch.float32, device=kp.device)
+    d.kp, d.shift, d.table, d.out = kp.data_ptr(), shift.data_ptr(), table.data_ptr(), out.data_ptr()
+    with torch.cuda.device(kp.device):
+        _lib.check(lib.p2c_heatmap_targets_fwd(ctypes.byref(d), _stream()), 'p2c_heatmap_targets_fwd')
+    return out
+
+
+def grouped_loss_tensor(pred: Tensor, gt: Tensor, mask: Optional[Tensor], criterion, group_dim: int):
+    """``BasePoseLoss``'s ``sum_per_frame`` (``group_dim=1``) / ``sum_per_joint`` (``group_dim=-2``) without boolean gathers:
+    ``pred`` and ``gt`` (B,T,K,D), ``mask`` (B,T,K) or None; per group the criterion over the selected (.., D) rows, groups whose
+    value is NaN (nothing selected under 'mean', or a NaN inside) skipped with zero gradient, the rest summed. Where the
+    reference raises on an empty ``torch.stack`` (every group skipped) the result is 0."""
+    import copy
+    each = copy.copy(criterion)
+    each.reduction = 'none'
+    mean = getattr(criterion, 'reduction', 'mean') == 'mean'
+    group_dim = group_dim % pred.ndim
+    others = [d for d in range(pred.ndim - 1) if d != group_dim]
+    sel = torch.ones(pred.shape[:-1], dtype=torch.bool, device=pred.device) if mask is None else mask.bool()
+    count = sel.sum(others).to(pred.dtype) * pred.shape[-1]
+
+    def per_group(w, count):
+        p = torch.where(w[..., None], pred, gt.detach())          # an unselected row never meets the criterion's backward
+        e = torch.where(w[..., None], each(p, gt), torch.zeros((), dtype=pred.dtype, device=pred.device))
+        s = e.sum(-1).sum(others)
+        return s / count if mean else s
+    with torch.no_grad():
+        use = ~torch.isnan(per_group(sel, count))               # 0 / 0 where nothing is selected under 'mean'
+    shape = [1] * (pred.ndim - 1)
+    shape[group_dim] = -1
+    w = sel & use.reshape(shape)
+    terms = per_group(w, count.clamp(min=1))
+    return torch.where(use, terms, torch.zeros_like(terms)).sum(), sel
+
+
+def _hm_channels(pred: Tensor, gt: Tensor, pred_channels, gt_channels, forced: int):
+    pc, gc = [int(c) for c in pred_channels], [int(c) for c in gt_channels]
+    if pred.ndim != 5 or gt.ndim != 5 or pred.shape[:2] != gt.shape[:2] or pred.shape[3:] != gt.shape[3:]:
+        raise RuntimeError(f'heatmaps_loss: prediction {tuple(pred.shape)} against target {tuple(gt.shape)}; (B,T,P,h,w) maps '
+                           'of one resolution expected')
+    if (len(pc) != len(gc) or not pc or any(not 0 <= c < pred.shape[2] for c in pc) or any(not 0 <= c < gt.shape[2] for c in gc)
+            or not -1 <= int(forced) < len(pc)):
+        raise RuntimeError(f'heatmaps_loss: channel lists {pc} / {gc} (forced {forced}) for {pred.shape[2]} / {gt.shape[2]} maps')
+    return pc, gc
+
+
+def _heatmaps_loss_tensor(pred: Tensor, gt: Tensor, pc, gc, forced: int, mask: bool):
+    cp, cg = pred[:, :, pc].flatten(3), gt[:, :, gc].flatten(3).to(pred.dtype)
+    sel = None
+    if mask:
+        sel = (cg != 0).all(-1)
+        if forced >= 0:
+            sel[..., forced] = True
+    return grouped_loss_tensor(cp, cg, sel, torch.nn.MSELoss(reduction='mean'), 1)
+
+
+def heatmaps_loss_supported(pred: Tensor, gt: Tensor, n_pairs: int) -> bool:
+    """What K28b covers: fp32 device maps outside autocast, at most 64 maps a frame on either side and at most 64 pairs."""
+    return (_hm_kernel_ok(pred, gt) and pred.ndim == 5 and gt.ndim == 5 and max(pred.shape[2], gt.shape[2], n_pairs) <= _lib.HEATMAPS_MAX_MAPS
+            and pred.numel() > 0)
+
+
+def _hm_loss_desc(pred, gt, pc, gc, forced, mask):
+    d = _lib.HeatmapsLossDesc()
+    d.B, d.T, d.Pp, d.Pg, d.h, d.w = pred.shape[0], pred.shape[1], pred.shape[2], gt.shape[2], pred.shape[3], pred.shape[4]
+    d.K, d.forced, d.mask = len(pc), int(forced), int(bool(mask))
+    for i, (a, b) in enumerate(zip(pc, gc)):
+        d.pred_channels[i], d.gt_channels[i] = a, b
+    d.pred, d.gt = pred.data_ptr(), gt.data_ptr()
+    return d
+
+
+class HeatmapsLossFunction(torch.autograd.Function):
+    """(loss, selection flags) = K28b(pred, gt): two launches forward (per-pair sums and flags, then the fixed-order finish),
+    one backward that reads the saved per-frame coefficients and flags. The gradient goes to the prediction only."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, pc, gc, forced: int, mask: bool):
+        lib = _lib.lib()
+        pred, gt = _require_device(pred, 'heatmaps'), _require_device(gt, 'target heatmaps')   # views are copied dense
+        B, T = pred.shape[:2]
+        f32 = dict(dtype=torch.float32, device=pred.device)
+        partials, coef, loss = torch.empty(B, T, len(pc), **f32), torch.empty(T, **f32), torch.empty(1, **f32)
+        flags = torch.empty(B, T, len(pc), dtype=torch.int32, device=pred.device)
+        d = _hm_loss_desc(pred, gt, pc, gc, forced, mask)
+        d.partials, d.flags, d.coef, d.loss = partials.data_ptr(), flags.data_ptr(), coef.data_ptr(), loss.data_ptr()
+        with torch.cuda.device(pred.device):
+            _lib.check(lib.p2c_heatmaps_loss_fwd(ctypes.byref(d), _stream()), 'p2c_heatmaps_loss_fwd')
+        ctx.save_for_backward(pred, gt, partials, flags, coef)
+        ctx.cfg = (pc, gc, forced, mask)
+        ctx.mark_non_differentiable(flags)
+        return loss.reshape(()), flags
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_flags):
+        lib = _lib.lib()
+        pred, gt, partials, flags, coef = ctx.saved_tensors
+        g_loss = _require_device(g_loss, 'grad').reshape(1)       # (a local: an expanded scalar is copied, the copy outlives the launch)
+        gp = torch.empty_like(pred)
+        d = _hm_loss_desc(pred, gt, *ctx.cfg)
+        d.partials, d.flags, d.coef = partials.data_ptr(), flags.data_ptr(), coef.data_ptr()
+        d.grad_loss, d.grad_pred = g_loss.data_ptr(), gp.data_ptr()
+        with torch.cuda.device(pred.device):
+            _lib.check(lib.p2c_heatmaps_loss_bwd(ctypes.byref(d), _stream()), 'p2c_heatmaps_loss_bwd')
+        return gp, None, None, None, None, None
+
+
+def heatmaps_loss(pred: Tensor, gt: Tensor, pred_channels: Sequence[int], gt_channels: Sequence[int], forced: int = -1,
+                  mask: bool = True, with_flags: bool = False):
+    """``HeatmapsLoss`` = ``BasePoseLoss``'s ``sum_per_frame`` with ``MSELoss('mean')`` over heatmaps: pair k compares the stored
+    channel ``pred_channels[k]`` of ``pred`` (B,T,Pp,h,w) with ``gt_channels[k]`` of ``gt`` (B,T,Pg,h,w); it is selected in (b,t)
+    when ``mask`` is off, when every cell of its target map is != 0, or when ``k == forced``; loss = sum over the frames of
+    S_t / (n_t h w), frames with nothing selected or a NaN sum skipped (zero gradient there). K28b on fp32 device tensors, the
+    tensor restatement otherwise. ``with_flags`` also returns the (B,T,K) selection."""
+    pc, gc = _hm_channels(pred, gt, pred_channels, gt_channels, forced)
+    if heatmaps_loss_supported(pred, gt, len(pc)):
+        loss, flags = HeatmapsLossFunction.apply(pred, gt, tuple(pc), tuple(gc), int(forced), bool(mask))
+        flags = flags.bool()
+    else:
+        loss, flags = _heatmaps_loss_tensor(pred, gt, pc, gc, int(forced), bool(mask))
+    return (loss, flags) if with_flags else loss
+
+
+def _heatmap_keypoints_tensor(heatmaps: Tensor, frame_size) -> Tensor:
+    B, T, P, h, w = heatmaps.shape
+    sw, sh = frame_size[0] / w, frame_size[1] / h
+    m = heatmaps[:, :, 1:].flatten(3)
+    c = m.max(-1).values                                            # NaN if the map holds one: c > 0 is false then
+    cells = torch.arange(h * w, device=m.device)
+    first = torch.where(m == c[..., None], cells, torch.full_like(cells, h * w)).min(-1).values.clamp_(max=h * w - 1)
+    row, col = torch.div(first, w, rounding_mode='floor'), first % w
+    out = torch.stack((col.float() * sw, row.float() * sh, c.float()), -1)
+    return torch.where((c > 0)[..., None], out, torch.zeros_like(out))
+
+
+def heatmap_keypoints(heatmaps: Tensor, frame_size) -> Tensor:
+    """The reference's ``_keypoints_from_heatmaps``: (B,T,P-1,3) = (col * sw, row * sh, c) of the maximum c of every map of
+    channels 1..P-1 at its first flat index when c > 0, zeros otherwise (a map with a NaN too), fp32. ``frame_size`` is
+    ``frames.shape[-2:]`` and is read as the reference reads it, (bbox_width, bbox_height): sw = frame_size[0] / w,
+    sh = frame_size[1] / h -- swapped for non-square frames, kept for parity. K28c (one launch, no host sync) on fp32 device
+    tensors with at most 64 maps, the tensor restatement otherwise."""
+    if heatmaps.ndim != 5 or heatmaps.shape[2] < 2 or heatmaps.shape[3] * heatmaps.shape[4] < 1:
+        raise RuntimeError(f'heatmap_keypoints: (B,T,P>=2,h,w) expected, got {tuple(heatmaps.shape)}')
+    B, T, P, h, w = heatmaps.shape
+    if not (_hm_kernel_ok(heatmaps) and P <= _lib.HEATMAPS_MAX_MAPS):
+        return _heatmap_keypoints_tensor(heatmaps, frame_size)
+    lib = _lib.lib()
+    maps = heatmaps.detach().contiguous()
+    out = torch.empty(B, T, P - 1, 3, dtype=torch.float32, device=maps.device)
+    d = _lib.HeatmapKeypointsDesc()
+    d.N, d.P, d.h, d.w, d.sw, d.sh = B * T, P, h, w, frame_size[0] / w, frame_size[1] / h
+    d.maps, d.out = maps.data_ptr(), out.data_ptr()
+    with torch.cuda.device(maps.device):
+        _lib.check(lib.p2c_heatmap_keypoints_fwd(ctypes.byref(d), _stream()), 'p2c_heatmap_keypoints_fwd')
+    return out
