@@ -545,6 +545,27 @@ typedef struct p2c_adamw_desc {
 } p2c_adamw_desc;
 P2C_API int p2c_adamw_step(const p2c_adamw_desc *desc, void *stream);
 
+/* ---- K29: the same step with the gradient clipped first (csrc/p2c_grad_clip.hip) ----------------------------------------
+ * Replaces torch.nn.utils.clip_grad_norm_ / clip_grad_value_ followed by optimizer.step() -- what Lightning does for the
+ * reference's --gradient_clip_val / --gradient_clip_algorithm (modeling.py:275, 353) -- on the flat buffer, without a host sync:
+ *   NORM:  total_norm = (float)(grad_scale * sqrt(sum of g^2 in double));  coef = min(bound / (total_norm + 1e-6f), 1), NaN kept;
+ *          g' = (g * grad_scale) * coef.        Two launches: the squared-norm partials, then the step.
+ *   VALUE: g' = clamp(g * grad_scale, -bound, bound), NaN kept.  One launch.
+ * followed by the update rule above on g' (grad_scale already applied: average first, then clip, as a data-parallel torch run
+ * does). The sum's order depends on n alone: the same data gives the same bits. `bound` is a HOST value: a captured graph
+ * bakes it in (re-capture to change it); everything else that varies between steps is read from device memory as above.
+ * Same checks as p2c_adamw_step, then P2C_E_ENUM for another mode, P2C_E_SHAPE for a bound that is not finite or not > 0,
+ * P2C_E_NULL for missing NORM pointers; n == 0 returns 0 and launches nothing. Graph-capturable. */
+enum { P2C_CLIP_NORM = 1, P2C_CLIP_VALUE = 2 };
+typedef struct p2c_clip_desc {
+  int32_t mode;         /* P2C_CLIP_* */
+  float   bound;        /* max_norm (2-norm) or clip_value; finite, > 0 */
+  double *partials;     /* NORM: device, p2c_grad_clip_partials(n) doubles; VALUE: NULL */
+  float  *total_norm;   /* NORM: device scalar, written by every call; VALUE: NULL */
+} p2c_clip_desc;
+P2C_API int64_t p2c_grad_clip_partials(int64_t n);
+P2C_API int p2c_adamw_step_clipped(const p2c_adamw_desc *desc, const p2c_clip_desc *clip, void *stream);
+
 /* ---- K11: dataset-side input pipeline for a batch of clips, one launch -------------------
  * Replaces, per clip and on the CPU in the reference, BaseDataset.__getitem__ (data/base/base_dataset.py:206-234):
  *   Projection2DMixin.process_projection_2d   data/base/mixins/dataset/projection_2d_mixin.py:209-232

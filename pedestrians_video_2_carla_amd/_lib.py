@@ -67,6 +67,14 @@ class AdamWDesc(ctypes.Structure):
                 ('zero_grad', ctypes.c_int32), ('scatter_idx', _f32p), ('scatter_dst', _f32p)]
 
 
+P2C_CLIP_NORM, P2C_CLIP_VALUE = 1, 2
+
+
+class ClipDesc(ctypes.Structure):
+    """p2c_clip_desc (include/p2c.h)."""
+    _fields_ = [('mode', ctypes.c_int32), ('bound', ctypes.c_float), ('partials', _f32p), ('total_norm', _f32p)]
+
+
 class GemmDesc(ctypes.Structure):
     """p2c_gemm_desc (include/p2c.h)."""
     _fields_ = [('M', ctypes.c_int32), ('N', ctypes.c_int32), ('K', ctypes.c_int32), ('trans_b', ctypes.c_int32),
@@ -234,6 +242,8 @@ SYMBOLS = {
     'p2c_mlp_pack': (ctypes.c_int, [ctypes.POINTER(MlpDesc), _vp]),
     'p2c_mlp_image_index': (_i64, [ctypes.POINTER(MlpDesc), _ip, _i64]),
     'p2c_adamw_step': (ctypes.c_int, [ctypes.POINTER(AdamWDesc), _vp]),
+    'p2c_grad_clip_partials': (_i64, [_i64]),
+    'p2c_adamw_step_clipped': (ctypes.c_int, [ctypes.POINTER(AdamWDesc), ctypes.POINTER(ClipDesc), _vp]),
     'p2c_collate_fwd': (ctypes.c_int, [ctypes.POINTER(CollateDesc), _vp]),
     'p2c_collate_mixed_fwd': (ctypes.c_int, [ctypes.POINTER(CollateMixedDesc), _vp]),
     'p2c_lstm_rec_fwd': (ctypes.c_int, [ctypes.POINTER(LstmDesc), _vp]),

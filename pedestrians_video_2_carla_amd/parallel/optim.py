@@ -6,7 +6,9 @@ With every parameter a view of one flat buffer (parallel/flat.py) the step is a 
   * step counter and hyper-parameters live in device memory -> the launch can be captured in a HIP graph and still follow
     an LR scheduler (``param_groups[0]['lr']`` is re-uploaded when it changes);
   * the 1/world_size gradient averaging of data-parallel training (``grad_scale``) and next step's ``zero_grad`` are
-    folded into the same pass.
+    folded into the same pass;
+  * ``set_clip`` folds torch.nn.utils.clip_grad_norm_ / clip_grad_value_ into it as well (K29, csrc/p2c_grad_clip.hip): the
+    norm is reduced on the device, never read on the host, and the launches stay capturable.
 ``state_dict()`` has torch's layout (``step``, ``exp_avg``, ``exp_avg_sq``) for ONE flat parameter: it is interchangeable with a
 torch.optim.AdamW built over the same flat tensor, NOT with the reference's per-parameter optimizer state (there the moments
 are one pair per module parameter; slicing the flat moments by ``FlatParameters.params`` offsets converts between the two).
@@ -35,6 +37,9 @@ class FlatAdamW(torch.optim.Optimizer):
         self.fused_steps_applied = 0              # bumped by every backward that applied this optimizer's step itself
         self._uploaded = None
         self._scatter = None                      # (int32 index per parameter, destination buffer) or None
+        self._clip = None                         # (mode, bound) or None
+        self._clip_partials = None                # norm mode: one double per workgroup of the squared-norm launch
+        self.last_grad_norm = None                # norm mode: device scalar, the last step's total norm (never synced)
         self._hyper = torch.zeros(6, dtype=torch.float32, device=p.device)
         self._ticket = torch.zeros(1, dtype=torch.int32, device=p.device)
         self.state[p] = {'step': torch.zeros((), dtype=torch.float32, device=p.device),
@@ -70,6 +75,40 @@ class FlatAdamW(torch.optim.Optimizer):
             raise ValueError('scatter index: one int32 per parameter, on the device')
         self._scatter = (index.contiguous(), dst)
 
+    def set_clip(self, value, algorithm: str = 'norm'):
+        """Clip the gradient inside the optimizer launch: ``'norm'`` = clip_grad_norm_(max_norm=value) (2-norm of the whole
+        flat gradient, after the ``grad_scale`` averaging), ``'value'`` = clip_grad_value_(clip_value=value). ``None`` / ``0``
+        turn it off. The bound is a host value: a graph captured with it keeps it."""
+        if algorithm not in ('norm', 'value'):
+            raise ValueError(f"gradient clip algorithm must be 'norm' or 'value', not {algorithm!r}")
+        if value is None or float(value) == 0.0:
+            self._clip, self.last_grad_norm = None, None
+            return
+        value = float(value)
+        if not (value > 0.0 and value != float('inf')):
+            raise ValueError(f'gradient clip value must be finite and positive, not {value!r}')
+        (p,) = self.param_groups[0]['params']
+        if algorithm == 'norm':
+            n_partials = int(_lib.lib().p2c_grad_clip_partials(p.numel()))
+            if self._clip_partials is None or self._clip_partials.numel() < n_partials:
+                self._clip_partials = torch.empty(max(n_partials, 1), dtype=torch.float64, device=p.device)
+            if self.last_grad_norm is None:
+                self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=p.device)
+            self._clip = (_lib.P2C_CLIP_NORM, value)
+        else:
+            self._clip, self.last_grad_norm = (_lib.P2C_CLIP_VALUE, value), None
+
+    def _clip_descriptor(self):
+        key = (self._clip, None if self._clip_partials is None else self._clip_partials.data_ptr(),
+               None if self.last_grad_norm is None else self.last_grad_norm.data_ptr())
+        if getattr(self, '_clip_desc_key', None) != key:
+            c = _lib.ClipDesc()
+            c.mode, c.bound = self._clip
+            if c.mode == _lib.P2C_CLIP_NORM:
+                c.partials, c.total_norm = self._clip_partials.data_ptr(), self.last_grad_norm.data_ptr()
+            self._clip_desc, self._clip_desc_key = c, key
+        return self._clip_desc
+
     def _descriptor(self, p):
         """The launch descriptor only holds addresses of long-lived buffers: built once, rebuilt if one of them moves."""
         st = self.state[p]
@@ -91,6 +130,9 @@ class FlatAdamW(torch.optim.Optimizer):
     def descriptor_for_fusion(self):
         """Launch descriptor for a kernel that applies this optimizer's step itself (p2c_mlp_desc.fused_adamw)."""
         (p,) = self.param_groups[0]['params']
+        if self._clip is not None:
+            raise RuntimeError('FlatAdamW: a gradient clip is set; a fused update cannot honour it (the norm has to be known '
+                               'before the first parameter is touched)')
         if not torch.cuda.is_current_stream_capturing():
             self.sync_hyper()
         elif self._uploaded is None:
@@ -121,6 +163,10 @@ class FlatAdamW(torch.optim.Optimizer):
             raise RuntimeError('FlatAdamW: call sync_hyper() (or one eager step) before capturing a graph')
         d = self._descriptor(p)
         with torch.cuda.device(p.device):
-            _lib.check(_lib.lib().p2c_adamw_step(ctypes.byref(d), torch.cuda.current_stream(p.device).cuda_stream),
-                       'p2c_adamw_step')
+            stream = torch.cuda.current_stream(p.device).cuda_stream
+            if self._clip is not None:
+                _lib.check(_lib.lib().p2c_adamw_step_clipped(ctypes.byref(d), ctypes.byref(self._clip_descriptor()), stream),
+                           'p2c_adamw_step_clipped')
+            else:
+                _lib.check(_lib.lib().p2c_adamw_step(ctypes.byref(d), stream), 'p2c_adamw_step')
         return loss

@@ -11,6 +11,9 @@ Two execution modes:
     batch, as bench.py does) stages nothing. With more than one rank the gradient all-reduce is captured into the
     step graph when every rank can do so, otherwise it stays outside (capture A: forward + backward; eager RCCL
     all-reduce; optimizer launch).
+``gradient_clip_val`` / ``gradient_clip_algorithm`` are Lightning's arguments of the same names: the clip runs inside FlatAdamW's
+launches (K29, csrc/p2c_grad_clip.hip) -- after the all-reduce, so the averaged gradient is what is clipped -- or through
+torch.nn.utils.clip_grad_* for any other optimizer; with a clip the optimizer is never fused into a backward.
 """
 import contextlib
 import os
@@ -64,7 +67,17 @@ def ranks_agree(ok: bool, device, checksum: Optional[torch.Tensor] = None, group
 
 class Trainer:
     def __init__(self, max_steps: int = 100, use_graph: bool = False, device: Optional[torch.device] = None,
-                 flatten: bool = True, log_every_n_steps: int = 0, steps_per_epoch: Optional[int] = None):
+                 flatten: bool = True, log_every_n_steps: int = 0, steps_per_epoch: Optional[int] = None,
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = 'norm'):
+        # Lightning's names and defaults (the reference's trainer takes them from argparse, modeling.py:275, 353): None / 0 = off
+        if gradient_clip_algorithm not in ('norm', 'value'):
+            raise ValueError(f"gradient_clip_algorithm must be 'norm' or 'value', not {gradient_clip_algorithm!r}")
+        if gradient_clip_val is not None and not (0.0 <= float(gradient_clip_val) < float('inf')):
+            raise ValueError(f'gradient_clip_val must be finite and not negative, not {gradient_clip_val!r}')
+        self.gradient_clip_val = float(gradient_clip_val) if gradient_clip_val else None
+        self.gradient_clip_algorithm = gradient_clip_algorithm
+        self.last_grad_norm: Optional[torch.Tensor] = None      # norm mode, after a step: a device scalar nothing syncs on
+        self._clip_in_kernel = False
         self.max_steps = max_steps
         self.use_graph = use_graph
         self.device = device
@@ -124,11 +137,21 @@ class Trainer:
             self._packed = [m for m in flow.modules() if hasattr(m, 'manage_packed_image')
                             and m.manage_packed_image(self.flat.flat_param, opt)]
             # single GPU: a module that owns every parameter can apply the optimizer step inside its own backward
-            self._opt_in_backward = (not self.exchange.enabled and os.environ.get('P2C_FUSED_UPDATE', '1') == '1'
+            # (a gradient clip needs the global norm before the first parameter is touched: no module is offered the optimizer)
+            self._opt_in_backward = (self.gradient_clip_val is None
+                                     and not self.exchange.enabled and os.environ.get('P2C_FUSED_UPDATE', '1') == '1'
                                      and any(m.accept_fused_optimizer(opt, self.flat.flat_param) for m in self._packed
                                              if hasattr(m, 'accept_fused_optimizer')))
             self._fused_seen = getattr(opt, 'fused_steps_applied', 0)
-            if hasattr(opt, 'grad_scale') and self.exchange.enabled:    # FlatAdamW folds the DP averaging into its pass
+            # K29: FlatAdamW clips inside its own launches; any other optimizer (another class, host tensors) and
+            # P2C_CLIP_FRAMEWORK=1 (timing comparisons) take torch.nn.utils.clip_grad_* in _optimizer_step
+            self._clip_in_kernel = (self.gradient_clip_val is not None and hasattr(opt, 'set_clip')
+                                    and os.environ.get('P2C_CLIP_FRAMEWORK', '0') != '1')
+            if self._clip_in_kernel:
+                opt.set_clip(self.gradient_clip_val, self.gradient_clip_algorithm)
+            framework_clip = self.gradient_clip_val is not None and not self._clip_in_kernel
+            # FlatAdamW folds the DP averaging into its pass (the tensor-path clip needs the averaged gradient itself)
+            if hasattr(opt, 'grad_scale') and self.exchange.enabled and not framework_clip:
                 opt.grad_scale = 1.0 / self.exchange.world
                 self.exchange.average_here = False
         else:
@@ -204,8 +227,16 @@ class Trainer:
             if applied != self._fused_seen:
                 self._fused_seen = applied
                 return
+        if self.gradient_clip_val is not None and not self._clip_in_kernel:
+            params = [p for o in self.optimizers for g in o.param_groups for p in g['params'] if p.grad is not None]
+            if self.gradient_clip_algorithm == 'norm':
+                self.last_grad_norm = torch.nn.utils.clip_grad_norm_(params, self.gradient_clip_val)
+            else:
+                torch.nn.utils.clip_grad_value_(params, self.gradient_clip_val)
         for o in self.optimizers:
             o.step()
+        if self._clip_in_kernel:
+            self.last_grad_norm = self.optimizers[0].last_grad_norm
 
     # ---- static batch (graph mode) -----------------------------------------------------------------------------------
     @staticmethod
@@ -402,12 +433,20 @@ class Trainer:
         # graph -- found with NaN-filled torch.empty (tests/conftest.py P2C_POISON_EMPTY), visible without it as parameters that
         # drift from the eager trainer by ~lr per step
         side = self._capture_stream = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
+        outer = torch.cuda.current_stream()
+        side.wait_stream(outer)
         with torch.cuda.stream(side):                 # warm-up outside capture (allocator, lazy inits, autotuning)
             for _ in range(3):
                 self._forward_backward(flow, batch, batch_idx, batch_start=False)
                 if distributed:
-                    self.exchange.all_reduce_gradients()
+                    # NOT on the side stream: a blocking collective runs on the stream it is issued from, and the process
+                    # group's watchdog thread keeps polling its completion event for up to one more period (~100 ms) after it
+                    # finished. An event last recorded on a stream that is capturing by then cannot be queried
+                    # (hipErrorCapturedEvent): the watchdog throws and the process aborts. Seen once in stage A's capture below.
+                    outer.wait_stream(side)
+                    with torch.cuda.stream(outer):
+                        self.exchange.all_reduce_gradients()
+                    side.wait_stream(outer)
                 self._optimizer_step()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
@@ -426,7 +465,7 @@ class Trainer:
             if self._kept_graph:
                 self._graph_nodes = self._count_nodes(g_fb)      # stage A alone: forward + backward
                 g_fb.instantiate()
-            if all(hasattr(o, '_descriptor') for o in self.optimizers):
+            if all(hasattr(o, '_descriptor') for o in self.optimizers) and self.gradient_clip_val is None:
                 g_opt = 'eager'          # FlatAdamW is a single kernel: a direct launch has less latency than a 1-node graph
             else:
                 g_opt = torch.cuda.CUDAGraph()
