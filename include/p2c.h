@@ -958,6 +958,23 @@ P2C_API int p2c_heatmaps_loss_fwd(const p2c_heatmaps_loss_desc *desc, void *stre
 P2C_API int p2c_heatmaps_loss_bwd(const p2c_heatmaps_loss_desc *desc, void *stream);
 P2C_API int p2c_heatmap_keypoints_fwd(const p2c_heatmap_keypoints_desc *desc, void *stream);
 
+/* ---- predicted poses <-> CARLA bone transforms (K30, csrc/p2c_carla_pose.hip) ---------------------------------------------------
+ * What the reference does per frame on the host (walker_control/p3d_pose.py:56-96 tensors_to_pose, :34-54 pose_to_tensors,
+ * renderers/carla_renderer.py:165-183 for the root), for N = B T frames of J >= 1 bones in one launch each way. fp32.
+ * p2c_carla_pose_fwd: rel_loc (N,J,3), rel_rot (N,J,3,3) -> bones (N,J,6); world_loc (N,3), world_rot (N,3,3) -- both null or
+ *   both given -- -> root (N,6), written in the same launch and only when they are given. A row is (x, y, -z, pitch, yaw, roll),
+ *   locations unscaled, with e = the 'XYZ' Euler angles of R = Rx(e0) Ry(e1) Rz(e2):  e1 = asin(R[0,2] clamped to [-1, 1]),
+ *   e0 = atan2(-R[1,2], R[2,2]), e2 = atan2(-R[0,1], R[0,0]);  pitch = -deg(e1), yaw = -deg(e2), roll = -deg(e0).
+ * p2c_carla_pose_inv: bones (N,J,6) -> loc (N,J,3) = (x, y, -z), rot (N,J,3,3) = Rx Ry Rz of rad(-roll, -pitch, -yaw).
+ * max_blocks  0: the kernels' own grid cap; > 0 lowers it (a test reaches the grid-stride regime with a handful of rows).
+ * No masking: a NaN operand gives NaN in the outputs computed from it and nowhere else. Every output element has one writer and
+ * nothing is reduced: two runs give the same bits. N = 0: nothing is launched. N < 0, J < 1, max_blocks < 0: P2C_E_SHAPE;
+ * a missing tensor, or one world input without the other: P2C_E_NULL; both before any launch. */
+P2C_API int p2c_carla_pose_fwd(const float *rel_loc, const float *rel_rot, const float *world_loc, const float *world_rot,
+                               float *bones, float *root, int64_t N, int32_t J, int32_t max_blocks, void *stream);
+P2C_API int p2c_carla_pose_inv(const float *bones, float *loc, float *rot, int64_t N, int32_t J, int32_t max_blocks,
+                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -318,6 +318,8 @@ SYMBOLS = {
     'p2c_heatmaps_loss_fwd': (ctypes.c_int, [ctypes.POINTER(HeatmapsLossDesc), _vp]),
     'p2c_heatmaps_loss_bwd': (ctypes.c_int, [ctypes.POINTER(HeatmapsLossDesc), _vp]),
     'p2c_heatmap_keypoints_fwd': (ctypes.c_int, [ctypes.POINTER(HeatmapKeypointsDesc), _vp]),
+    'p2c_carla_pose_fwd': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
+    'p2c_carla_pose_inv': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,44 @@
+"""Predictions as a CARLA animation file: what a player script feeds to a walker, frame by frame.
+
+One ``.npz`` with ``bones`` (N,T,J,6) and ``root`` (N,T,6) -- rows of (x, y, z, pitch, yaw, roll), metres and degrees, CARLA's
+axes, see ``ops.carla_pose_export`` -- ``bone_names`` (J), ``age`` / ``gender`` (N: which walker blueprint a clip belongs to)
+and ``fps``. Playing it needs a CARLA server and is not part of this package.
+"""
+from typing import Dict
+
+import numpy as np
+
+from pedestrians_video_2_carla_amd.walker_control.carla_pose import BONE_NAMES, export_clips
+
+
+def save_carla_animation(path: str, outputs, fps: float = 30.0) -> str:
+    """``outputs``: the list ``Trainer.predict`` returns, ``(sliced, meta)`` per batch. Every batch is converted with one
+    ``carla_pose_export`` call and copied to the host once. Returns the path written (``.npz`` appended when missing)."""
+    outputs = list(outputs)
+    if not outputs:
+        raise ValueError('no predictions to save')
+    bones, roots, ages, genders = [], [], [], []
+    for sliced, meta in outputs:
+        b, r = export_clips(sliced)
+        if r is None:
+            raise KeyError('world_loc / world_rot are missing from the predictions: no root transform to store')
+        n = len(b)
+        bones.append(b)
+        roots.append(r)
+        ages.extend(str(a) for a in meta.get('age', ['adult'] * n))
+        genders.extend(str(g) for g in meta.get('gender', ['female'] * n))
+    bones, roots = np.concatenate(bones, 0), np.concatenate(roots, 0)
+    if bones.shape[-2] != len(BONE_NAMES):
+        raise ValueError(f'save_carla_animation: {bones.shape[-2]} bones, {len(BONE_NAMES)} expected')
+    if not str(path).endswith('.npz'):
+        path = str(path) + '.npz'
+    np.savez(path, bones=bones.astype(np.float32), root=roots.astype(np.float32), bone_names=np.array(BONE_NAMES),
+             age=np.array(ages), gender=np.array(genders), fps=np.float64(fps))
+    return str(path)
+
+
+def load_carla_animation(path: str) -> Dict[str, object]:
+    """The file back: arrays ``bones`` / ``root``, lists ``bone_names`` / ``age`` / ``gender``, float ``fps``."""
+    with np.load(path, allow_pickle=False) as f:
+        return {'bones': f['bones'], 'root': f['root'], 'bone_names': [str(s) for s in f['bone_names']],
+                'age': [str(s) for s in f['age']], 'gender': [str(s) for s in f['gender']], 'fps': float(f['fps'])}

@@ -3262,3 +3262,89 @@ def heatmap_keypoints(heatmaps: Tensor, frame_size) -> Tensor:
     with torch.cuda.device(maps.device):
         _lib.check(lib.p2c_heatmap_keypoints_fwd(ctypes.byref(d), _stream()), 'p2c_heatmap_keypoints_fwd')
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# predicted poses <-> CARLA bone transforms (K30, csrc/p2c_carla_pose.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def carla_framework() -> bool:
+    """P2C_CARLA_FRAMEWORK=1: ``carla_pose_export`` / ``carla_pose_import`` run their tensor definitions on the device (the
+    comparison arm of tools/bench_carla_pose.py)."""
+    return os.environ.get('P2C_CARLA_FRAMEWORK', '0') == '1'
+
+
+def _carla_kernel_ok(*tensors: Tensor) -> bool:
+    return (all(t.is_cuda and t.dtype == torch.float32 and t.device == tensors[0].device for t in tensors)
+            and not carla_framework() and not torch.is_autocast_enabled())
+
+
+def _carla_row(loc: Tensor, rot: Tensor) -> Tensor:
+    """(..., 3), (..., 3, 3) -> (..., 6) = (x, y, -z, pitch, yaw, roll): the tensor definition of K30's forward."""
+    from pedestrians_video_2_carla_amd.transforms.rotation_conversions import matrix_to_euler_angles
+    deg = -torch.rad2deg(matrix_to_euler_angles(rot, 'XYZ'))
+    return torch.stack((loc[..., 0], loc[..., 1], -loc[..., 2], deg[..., 1], deg[..., 2], deg[..., 0]), -1)
+
+
+def _carla_check_export(rel_loc, rel_rot, world_loc, world_rot):
+    if (rel_loc.ndim < 2 or rel_loc.shape[-1] != 3 or rel_rot.ndim != rel_loc.ndim + 1
+            or tuple(rel_rot.shape) != tuple(rel_loc.shape) + (3,) or rel_loc.shape[-2] < 1):
+        raise RuntimeError(f'carla_pose_export: locations {tuple(rel_loc.shape)} with rotations {tuple(rel_rot.shape)}; '
+                           '(...,J,3) with (...,J,3,3) expected')
+    if (world_loc is None) != (world_rot is None):
+        raise RuntimeError('carla_pose_export: world_loc and world_rot come together or not at all')
+    if world_loc is not None:
+        lead = tuple(rel_loc.shape[:-2])
+        if tuple(world_loc.shape) != lead + (3,) or tuple(world_rot.shape) != lead + (3, 3):
+            raise RuntimeError(f'carla_pose_export: world tensors {tuple(world_loc.shape)}, {tuple(world_rot.shape)} for poses '
+                               f'{tuple(rel_loc.shape)}; {lead + (3,)} and {lead + (3, 3)} expected')
+
+
+@torch.no_grad()
+def carla_pose_export(rel_loc: Tensor, rel_rot: Tensor, world_loc: Optional[Tensor] = None,
+                      world_rot: Optional[Tensor] = None, max_blocks: int = 0) -> Tuple[Tensor, Optional[Tensor]]:
+    """What a CARLA walker consumes, from what ``flow.predict_step`` leaves: ``rel_loc`` (...,J,3) and ``rel_rot`` (...,J,3,3)
+    -> ``bones`` (...,J,6), and ``world_loc`` (...,3) with ``world_rot`` (...,3,3) -> ``root`` (...,6) (None without them). A row is
+    (x, y, -z, pitch, yaw, roll) with (roll, pitch, yaw) = -degrees of ``matrix_to_euler_angles(R, 'XYZ')[(0, 1, 2)]`` --
+    the reference's ``P3dPose.tensors_to_pose`` and the root conversion of ``CarlaRenderer.render_frame``; locations are not
+    scaled. Any leading dimensions, any J >= 1; views are made contiguous. A predict-time operation: nothing is recorded for
+    autograd. fp32 device tensors outside autocast take K30 (one launch for bones and root); host tensors, fp64, other dtypes
+    and ``P2C_CARLA_FRAMEWORK=1`` take the tensor definition. ``max_blocks`` lowers the kernel's grid cap (tests)."""
+    _carla_check_export(rel_loc, rel_rot, world_loc, world_rot)
+    given = [t for t in (rel_loc, rel_rot, world_loc, world_rot) if t is not None]
+    if not _carla_kernel_ok(*given):
+        return _carla_row(rel_loc, rel_rot), (_carla_row(world_loc, world_rot) if world_loc is not None else None)
+    lib = _lib.lib()
+    loc, rot = rel_loc.detach().contiguous(), rel_rot.detach().contiguous()
+    wl = world_loc.detach().contiguous() if world_loc is not None else None
+    wr = world_rot.detach().contiguous() if world_rot is not None else None
+    n_joints = loc.shape[-2]
+    n = loc.numel() // (3 * n_joints)
+    bones = torch.empty(tuple(loc.shape[:-1]) + (6,), dtype=torch.float32, device=loc.device)
+    root = torch.empty(tuple(wl.shape[:-1]) + (6,), dtype=torch.float32, device=loc.device) if wl is not None else None
+    with torch.cuda.device(loc.device):
+        _lib.check(lib.p2c_carla_pose_fwd(loc.data_ptr(), rot.data_ptr(), _ptr(wl), _ptr(wr), bones.data_ptr(), _ptr(root),
+                                          n, n_joints, int(max_blocks), _stream()), 'p2c_carla_pose_fwd')
+    return bones, root
+
+
+@torch.no_grad()
+def carla_pose_import(bones: Tensor, max_blocks: int = 0) -> Tuple[Tensor, Tensor]:
+    """The inverse of ``carla_pose_export`` (the reference's ``P3dPose.pose_to_tensors``): ``bones`` (...,J,6) rows of
+    (x, y, z, pitch, yaw, roll) -> ``loc`` (...,J,3) = (x, y, -z) and ``rot`` (...,J,3,3) = ``euler_angles_to_matrix`` of
+    radians(-roll, -pitch, -yaw), 'XYZ'. Dispatch as ``carla_pose_export``."""
+    if bones.ndim < 2 or bones.shape[-1] != 6 or bones.shape[-2] < 1:
+        raise RuntimeError(f'carla_pose_import: (...,J,6) expected, got {tuple(bones.shape)}')
+    if not _carla_kernel_ok(bones):
+        from pedestrians_video_2_carla_amd.transforms.rotation_conversions import euler_angles_to_matrix
+        angles = torch.deg2rad(torch.stack((-bones[..., 5], -bones[..., 3], -bones[..., 4]), -1))
+        return (torch.stack((bones[..., 0], bones[..., 1], -bones[..., 2]), -1), euler_angles_to_matrix(angles, 'XYZ'))
+    lib = _lib.lib()
+    rows = bones.detach().contiguous()
+    n_joints = rows.shape[-2]
+    n = rows.numel() // (6 * n_joints)
+    loc = torch.empty(tuple(rows.shape[:-1]) + (3,), dtype=torch.float32, device=rows.device)
+    rot = torch.empty(tuple(rows.shape[:-1]) + (3, 3), dtype=torch.float32, device=rows.device)
+    with torch.cuda.device(rows.device):
+        _lib.check(lib.p2c_carla_pose_inv(rows.data_ptr(), loc.data_ptr(), rot.data_ptr(), n, n_joints, int(max_blocks),
+                                          _stream()), 'p2c_carla_pose_inv')
+    return loc, rot

@@ -683,6 +683,18 @@ class Trainer:
             flow.train(was_training)
         return flow.compute_metrics(sync=True)
 
+    def predict(self, flow, batches: Iterable) -> List:
+        """Lightning's predict loop over ``batches``: ``flow.predict_step(batch, i)`` (which runs the batch-start hook itself) in
+        eval mode and without gradients, issued eagerly; the flow's train / eval mode is put back afterwards. Returns the list
+        of ``(sliced, meta)`` -- what ``BaseDataModule.save_predictions`` and ``save_carla_animation`` take."""
+        was_training = flow.training
+        flow.eval()
+        try:
+            with torch.no_grad():
+                return [flow.predict_step(batch, i) for i, batch in enumerate(batches)]
+        finally:
+            flow.train(was_training)
+
     def fit(self, flow, datamodule, batches: Optional[Iterable] = None):
         self.setup(flow, datamodule)
         device = self.device or flow.device

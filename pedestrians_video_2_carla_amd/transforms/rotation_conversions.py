@@ -29,3 +29,21 @@ def euler_angles_to_matrix(euler_angles: Tensor, convention: str = 'XYZ') -> Ten
     def mm3(a, b):       # 3x3 products as element-wise work: the synthetic data module composes (B, T, 26) of them per batch,
         return (a.unsqueeze(-1) * b.unsqueeze(-3)).sum(-2)      # which as a batched library GEMM took ~1 ms per call
     return mm3(mm3(m[0], m[1]), m[2])
+
+
+def matrix_to_euler_angles(matrix: Tensor, convention: str = 'XYZ') -> Tensor:
+    """Inverse of ``euler_angles_to_matrix(., 'XYZ')`` above, R = Rx(a0) Ry(a1) Rz(a2) (the only convention the reference
+    ever asks for; any other raises): a1 = asin(R[0,2]), a0 = atan2(-R[1,2], R[2,2]), a2 = atan2(-R[0,1], R[0,0]); (..., 3, 3)
+    -> (..., 3). The middle angle comes back in [-90, 90] degrees: a matrix built from a middle angle beyond that range
+    returns its other Euler representation, which gives the same matrix.
+    One deliberate difference from pytorch3d: R[0,2] is clamped to [-1, 1] before the asin. An orthonormalised fp32 network
+    output can land one ulp outside that range, where pytorch3d returns NaN; here it is +-90 degrees. (torch.clamp lets a NaN
+    through, so a missing joint still gives NaN.)"""
+    if convention != 'XYZ':
+        raise ValueError(f"matrix_to_euler_angles: convention '{convention}' ('XYZ' is the only one implemented)")
+    if matrix.ndim < 2 or tuple(matrix.shape[-2:]) != (3, 3):
+        raise ValueError(f'matrix_to_euler_angles: (..., 3, 3) expected, got {tuple(matrix.shape)}')
+    a1 = torch.asin(torch.clamp(matrix[..., 0, 2], -1.0, 1.0))
+    a0 = torch.atan2(-matrix[..., 1, 2], matrix[..., 2, 2])
+    a2 = torch.atan2(-matrix[..., 0, 1], matrix[..., 0, 0])
+    return torch.stack((a0, a1, a2), -1)
