@@ -76,10 +76,10 @@ __global__ __launch_bounds__(64 * WAVES) void mlp_fwd_kernel(const MlpArgs a) {
   const int64_t n_tiles = (a.N + TS - 1) / TS;
   TileRegs xr;
   ImageRegs wr;
-  tile_issue(a.x, (int64_t)blockIdx.x * TS, a.N, sh.dims(0), a.vec_x != 0, xr);   // first tile, then the image behind it
+  tile_issue<NTH>(a.x, (int64_t)blockIdx.x * TS, a.N, sh.dims(0), a.vec_x != 0, xr);   // first tile, then the image behind it
   if constexpr (S::kStatic) stage_issue(a.w_image, total4, wr, 0, 0, issue_mark<S>(1));
   else stage_issue(a.w_image, total4, wr);
-  init_rows(H, sh.h_off(0) + sh.dims(0), sh.h_off(0) + k_rows(sh.dims(0)), sh.h_off(0) + sh.dims(0));
+  init_rows<NTH>(H, sh.h_off(0) + sh.dims(0), sh.h_off(0) + k_rows(sh.dims(0)), sh.h_off(0) + sh.dims(0));
   if constexpr (!S::kStatic) {
     stage_commit(total4, wr, lds);
     stage_rest(a.w_image, total4, wr, lds);
@@ -91,8 +91,8 @@ __global__ __launch_bounds__(64 * WAVES) void mlp_fwd_kernel(const MlpArgs a) {
     const int64_t row0 = tile * TS, row = row0 + L.c;
     const bool row_ok = row < a.N;
     TR(0, 2);
-    tile_commit(sh.dims(0), a.vec_x != 0, xr, H + sh.h_off(0) * TP);
-    tile_issue(a.x, (tile + gridDim.x) * TS, a.N, sh.dims(0), a.vec_x != 0, xr);    // prefetch the next tile of this block
+    tile_commit<NTH>(sh.dims(0), a.vec_x != 0, xr, H + sh.h_off(0) * TP);
+    tile_issue<NTH>(a.x, (tile + gridDim.x) * TS, a.N, sh.dims(0), a.vec_x != 0, xr);    // prefetch the next tile of this block
     for_layers(sh, 0, nl, [&](int l) {
       if constexpr (S::kStatic) {   // the image rounds this layer reads, as late as possible
         if constexpr (first) stage_commit(total4, wr, lds, 0, l == 0 ? 0 : rounds_upto<S>(l - 1), rounds_upto<S>(l));
@@ -231,21 +231,21 @@ __global__ __launch_bounds__(64 * WAVES) void mlp_bwd_kernel(const MlpArgs a) {
   float *G = H + (sh.h_off(nl) - sh.h_off(1)) * TP;          // G_l lives at row h_off(l) of this base (l = 1..L)
   TileRegs xr, gr;
   ImageRegs wr;
-  tile_issue(a.x, (int64_t)blockIdx.x * TS, a.N, sh.dims(0), a.vec_x != 0, xr);   // needed first; the image in layer
+  tile_issue<NTH>(a.x, (int64_t)blockIdx.x * TS, a.N, sh.dims(0), a.vec_x != 0, xr);   // needed first; the image in layer
   if constexpr (S::kStatic && !SAVED) stage_issue(a.w_image, total4, wr, 0, 0, issue_mark<S>(1));   // order behind it; gy (first
   else stage_issue(a.w_image, total4, wr);                                                // read by the dgrad chain) last
   if constexpr (static_layers<S>() < 4 || SAVED)
-    tile_issue(a.gy, (int64_t)blockIdx.x * TS, a.N, sh.dims(nl), a.vec_gy != 0, gr);
+    tile_issue<NTH>(a.gy, (int64_t)blockIdx.x * TS, a.N, sh.dims(nl), a.vec_gy != 0, gr);
   ActRegs ar;
   if constexpr (SAVED) {
     if constexpr (S::kStatic) acts_issue(sh, a, blockIdx.x, (a.N + TS - 1) / TS, ar);
     // rows the saved activations never overwrite: the constant-one row behind each H_l and the zero rows of the k rounding
     for_layers(sh, 1, nl, [&](int l) {
-      init_rows(H, sh.h_off(l) + sh.dims(l), sh.h_off(l) + act_rows_of(sh.dims(l)), sh.h_off(l) + sh.dims(l));
+      init_rows<NTH>(H, sh.h_off(l) + sh.dims(l), sh.h_off(l) + act_rows_of(sh.dims(l)), sh.h_off(l) + sh.dims(l));
     });
   }
-  init_rows(H, sh.h_off(0) + sh.dims(0), sh.h_off(0) + k_rows(sh.dims(0)), sh.h_off(0) + sh.dims(0));
-  init_rows(G, sh.h_off(nl) + sh.dims(nl), sh.h_off(nl) + pad16(sh.dims(nl)), -1);
+  init_rows<NTH>(H, sh.h_off(0) + sh.dims(0), sh.h_off(0) + k_rows(sh.dims(0)), sh.h_off(0) + sh.dims(0));
+  init_rows<NTH>(G, sh.h_off(nl) + sh.dims(nl), sh.h_off(nl) + pad16(sh.dims(nl)), -1);
   if constexpr (!S::kStatic) {
     stage_commit(total4, wr, lds);
     stage_rest(a.w_image, total4, wr, lds);
@@ -263,8 +263,8 @@ __global__ __launch_bounds__(64 * WAVES) void mlp_bwd_kernel(const MlpArgs a) {
     constexpr bool first = decltype(first_c)::value;
     const int64_t row0 = tile * TS;
     lds_barrier();                         // previous tile's dW phase has consumed H and G
-    tile_commit(sh.dims(0), a.vec_x != 0, xr, H + sh.h_off(0) * TP);
-    tile_issue(a.x, row0 + (int64_t)gridDim.x * TS, a.N, sh.dims(0), a.vec_x != 0, xr);   // prefetch this block's next tile
+    tile_commit<NTH>(sh.dims(0), a.vec_x != 0, xr, H + sh.h_off(0) * TP);
+    tile_issue<NTH>(a.x, row0 + (int64_t)gridDim.x * TS, a.N, sh.dims(0), a.vec_x != 0, xr);   // prefetch this block's next tile
     if constexpr (SAVED) {
       // ---- phase F replaced: H_1 .. H_{L-1} as the forward left them (bit-identical to a recomputation)
       TR(1, 2);
@@ -285,7 +285,7 @@ __global__ __launch_bounds__(64 * WAVES) void mlp_bwd_kernel(const MlpArgs a) {
         lds_barrier();
         if constexpr (S::kStatic && first) {
           stage_issue(a.w_image, total4, wr, 0, issue_mark<S>(l + 1), issue_mark<S>(l + 2));
-          if (static_layers<S>() >= 4 && l == 2) tile_issue(a.gy, row0, a.N, sh.dims(nl), a.vec_gy != 0, gr);   // behind the image
+          if (static_layers<S>() >= 4 && l == 2) tile_issue<NTH>(a.gy, row0, a.N, sh.dims(nl), a.vec_gy != 0, gr);   // behind the image
         }
         TR(1, 3 + l);
         layer_forward<P, S::kStatic>(L, lds + sh.w_off(l), sh.ld(l), sh.dims(l), sh.dims(l + 1), true, H + sh.h_off(l) * TP,
@@ -296,8 +296,8 @@ __global__ __launch_bounds__(64 * WAVES) void mlp_bwd_kernel(const MlpArgs a) {
         if constexpr (first) stage_commit(total4, wr, lds, 0, nl >= 2 ? rounds_upto<S>(nl - 2) : 0, STAGE_U);
       }
     }
-    tile_commit(sh.dims(nl), a.vec_gy != 0, gr, G + sh.h_off(nl) * TP);
-    tile_issue(a.gy, row0 + (int64_t)gridDim.x * TS, a.N, sh.dims(nl), a.vec_gy != 0, gr);
+    tile_commit<NTH>(sh.dims(nl), a.vec_gy != 0, gr, G + sh.h_off(nl) * TP);
+    tile_issue<NTH>(a.gy, row0 + (int64_t)gridDim.x * TS, a.N, sh.dims(nl), a.vec_gy != 0, gr);
     // ---- phase D: G_l = relu'(H_l) .* (W_l^T G_{l+1}), l = L-1 .. 1
     for_layers_down(sh, nl - 1, 1, [&](int l) {
       lds_barrier();

@@ -298,17 +298,22 @@ __device__ __forceinline__ f32x4 mfma_k16(const float (&a)[4], const float (&b)[
 // 16 consecutive rows of a row-major [N][n] HBM matrix (one contiguous span) -> LDS transposed dst[k * TP + sample];
 // rows beyond N read as zero. ISSUE puts every load of the thread in flight, COMMIT (later, after other work) stores to
 // LDS: the HBM latency of the next tile hides behind the current tile's phases.
+// NT is the workgroup's thread count as a compile-time value, written at every call (NTH for a kernel launched with 64 * WAVES
+// threads): there is no default, a caller with another block size must say so. blockDim.x is no
+// constant even under __launch_bounds__: it is a 16-bit implicit kernel argument, fetched with a VECTOR load whose value the
+// LDS addresses then wait for -- behind every load issued before it.
 constexpr int TILE_UV = (TS * MAXW / 4 + 64 * WAVES - 1) / (64 * WAVES);   // float4 per thread (vector path)
 constexpr int TILE_US = (TS * MAXW + 64 * WAVES - 1) / (64 * WAVES);       // floats per thread (scalar path)
 static_assert(TILE_US <= 4 * TILE_UV, "scalar path must fit the vector path's registers");
 struct TileRegs {
   f32x4 v[TILE_UV];   // the scalar path keeps its floats in the same registers (v[u / 4][u % 4])
 };
+template <int NT>
 __device__ __forceinline__ void tile_issue(const float *src, int64_t row0, int64_t N, int n, bool vec, TileRegs &r) {
   const int64_t left = N - row0;
   const int valid = left <= 0 ? 0 : (int)(left < TS ? left : TS) * n;      // floats of this tile that exist
   const float *p = src + row0 * n;
-  const int nth = blockDim.x;
+  constexpr int nth = NT;
   if (vec) {                                               // n % 4 == 0: a float4 never straddles two rows
     const f32x4 *p4 = reinterpret_cast<const f32x4 *>(p);
 #pragma unroll
@@ -324,8 +329,9 @@ __device__ __forceinline__ void tile_issue(const float *src, int64_t row0, int64
     }
   }
 }
+template <int NT>
 __device__ __forceinline__ void tile_commit(int n, bool vec, const TileRegs &r, float *dst) {
-  const int nth = blockDim.x;
+  constexpr int nth = NT;
   if (vec) {
     const int total4 = (TS * n) >> 2;
 #pragma unroll
@@ -353,8 +359,9 @@ __device__ __forceinline__ void tile_commit(int n, bool vec, const TileRegs &r, 
 // Rows of the activation area that are READ but never written by a tile load or a layer epilogue must be finite (they
 // meet zero weights): the padding rows of H_0 behind the x tile (row n0 = the constant one) and, in the backward, the
 // padding rows of the gy tile. Everything else is rewritten for every tile before it is read.
+template <int NT>
 __device__ __forceinline__ void init_rows(float *area, int row0, int row1, int one_row) {
-  for (int i = row0 * TP + threadIdx.x; i < row1 * TP; i += blockDim.x) area[i] = (i / TP == one_row) ? 1.f : 0.f;
+  for (int i = row0 * TP + threadIdx.x; i < row1 * TP; i += NT) area[i] = (i / TP == one_row) ? 1.f : 0.f;
 }
 __device__ __forceinline__ int k_rows(int n_in) { return ((((n_in + 1 + 3) >> 2) + 3) & ~3) * 4; }   // rows behind the x tile kept finite
 // k-steps (of 4 rows each) of a layer's forward / dgrad loop. fp32 runs exactly the steps that carry data: a step beyond them

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(64 * WAVES) void relu_stack_fwd_kernel(const StackA
   const int nl = a.n_layers, n0 = a.dims[0], nL = a.dims[nl];
   float *H = lds + a.w_total;
   stage_images(a, lds);
-  init_rows(H, a.h_off[0] + n0, a.h_off[0] + k_rows(n0), a.h_off[0] + n0);     // the ones row and the k rounding behind the x tile
+  init_rows<NTH>(H, a.h_off[0] + n0, a.h_off[0] + k_rows(n0), a.h_off[0] + n0);     // the ones row and the k rounding behind the x tile
   const int64_t n_tiles = (a.N + TS - 1) / TS;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t row0 = tile * TS, row = row0 + L.c;
@@ -148,8 +148,8 @@ __global__ __launch_bounds__(64 * WAVES) void relu_stack_bwd_kernel(const StackA
   float *H = lds + a.w_total;
   float *G = H + (a.h_off[nl] - a.h_off[1]) * TP;            // G_l lives at row h_off[l] of this base (l = 1 .. L)
   stage_images(a, lds);
-  init_rows(H, a.h_off[0] + n0, a.h_off[0] + k_rows(n0), a.h_off[0] + n0);
-  init_rows(G, a.h_off[nl] + nL, a.h_off[nl] + pad16(nL), -1);   // rows of G_L the dgrad / dW phases read beyond the gy tile
+  init_rows<NTH>(H, a.h_off[0] + n0, a.h_off[0] + k_rows(n0), a.h_off[0] + n0);
+  init_rows<NTH>(G, a.h_off[nl] + nL, a.h_off[nl] + pad16(nL), -1);   // rows of G_L the dgrad / dW phases read beyond the gy tile
   const int lane_off = L.c * TP + L.g;
   f32x4 acc[MAX_SLOTS];
 #pragma unroll

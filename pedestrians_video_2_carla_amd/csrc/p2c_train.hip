@@ -99,6 +99,33 @@ __device__ __forceinline__ int image_ld(int l) {
   return r;
 }
 
+// Position of dW_aug tile t (the tile order of p2c_mlp::locate_tile) for the shape known at compile time: a cumulative compare
+// over the six layers' tile counts and a division by each layer's constant m-tile count -- straight scalar code with no loop, no
+// division by a run-time value and no table in memory, so the first factor load is not kept waiting for it.
+struct StaticTile {
+  int l, ntile, mtile;
+  int n_in, n_out;
+  int g_row, h_row;          // first factor row of G_{l+1} / H_l
+};
+__host__ __device__ constexpr int tiles_m(int l) { return (S::dim_at(l) + 1 + 15) >> 4; }
+__host__ __device__ constexpr int tiles_of(int l) { return ((S::dim_at(l + 1) + 15) >> 4) * tiles_m(l); }
+__host__ __device__ constexpr int tile_start(int l) {
+  int r = 0;
+  for (int i = 0; i < l; ++i) r += tiles_of(i);
+  return r;
+}
+__device__ __forceinline__ StaticTile locate_tile_static(int t) {
+  StaticTile r{0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < NLAY; ++i) {
+    const bool in = (i == 0 || t >= tile_start(i)) && (i == NLAY - 1 || t < tile_start(i + 1));   // (past the last tile: the last layer, as the loop)
+    const int rem = t - tile_start(i), nt = rem / tiles_m(i);
+    r.l = in ? i : r.l, r.ntile = in ? nt : r.ntile, r.mtile = in ? rem - nt * tiles_m(i) : r.mtile;
+    r.n_in = in ? S::dim_at(i) : r.n_in, r.n_out = in ? S::dim_at(i + 1) : r.n_out;
+    r.g_row = in ? f_g_off(i + 1) : r.g_row, r.h_row = in ? f_h_off(i) : r.h_row;
+  }
+  return r;
+}
 // inclusive scan over the frames of the clip, P_t = c_t c_{t-1} ... c_0 (the order of p2c::scan_time), ping-pong planes
 __device__ __forceinline__ ph::M3 scan_time2(ph::M3 P, int t, int j, int T, float *p0, float *p1) {
   float *cur = p0, *oth = p1;
@@ -188,8 +215,17 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   // ---- clip-independent set-up --------------------------------------------------------------------------------------------------
   // Persistent over clips: workgroup b walks clips b, b + gridDim.x, ... (grid = min(B, CUs)); the 84 KB weight image is staged
   // ONCE, during the first clip's forward. The first clip's x tile is requested first, then the image rounds.
+  // The first clip's skeleton type goes out ahead of everything: the reference-table addresses hang on it, and the tables
+  // are asked for behind layer 0's barrier, when it has long arrived (asked for where the tables are needed, it drained every
+  // load in flight and started a second, dependent trip). The index sits in a VGPR on purpose: a vector load travels beside
+  // the tile loads, a scalar one would come under the next kernel-argument wait.
+  auto skel_type_of = [&](int clip) {
+    asm volatile("" : "+v"(clip));
+    return d.skel_type[clip];
+  };
+  const int st_first = skel_type_of((int)blockIdx.x < d.B ? (int)blockIdx.x : 0);
   TileRegs xr;
-  tile_issue(m.x, (int64_t)blockIdx.x * T, (int64_t)blockIdx.x * T + T, S::dims(0), true, xr);
+  tile_issue<NTH>(m.x, (int64_t)blockIdx.x * T, (int64_t)blockIdx.x * T + T, S::dims(0), true, xr);
 #if P2C_TRAIN_DMA_IMAGE
   image_dma_issue(m.w_image, lds, L.wave, L.lane);
 #else
@@ -215,29 +251,27 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
     ph::fill_lane(PL, d);
   }
   const int jc = PL.j < ph::J ? PL.j : 0, tc = t < T ? t : T - 1;
+  // this lane's rows of skeleton type 0 in the two reference tables, formed with the entry fetches (taken where the tables are
+  // loaded, the table pointers were one more kernel-argument round trip behind layer 0's barrier)
+  typedef __attribute__((address_space(1))) const float gcfloat;
+  uintptr_t ref_loc_lane = (uintptr_t)(d.ref_rel_loc + jc * 3), ref_rot_lane = (uintptr_t)(d.ref_rel_rot + jc * 9);
+  asm volatile("" : "+v"(ref_loc_lane), "+v"(ref_rot_lane));
   // pair counts: issued now, consumed after the first clip's MLP forward (no add here: an add would wait for every load above)
   const float c0raw = m.counts[(int)threadIdx.x < d.B ? threadIdx.x : 0];
   const float c1raw = m.counts[(int)threadIdx.x + NTH < d.B ? threadIdx.x + NTH : 0];
   if (blockIdx.x == 0 && (int)threadIdx.x < m.n_counters) m.counters[threadIdx.x] = 0;   // arrival tickets of train_wgrad_kernel
-  init_rows(H, S::h_off(0) + S::dims(0), S::h_off(0) + k_rows(S::dims(0)), S::h_off(0) + S::dims(0));
+  init_rows<NTH>(H, S::h_off(0) + S::dims(0), S::h_off(0) + k_rows(S::dims(0)), S::h_off(0) + S::dims(0));
   float coef2 = 0.f, coef3 = 0.f;             // loss coefficients: the same for every clip, worked out in the first one
   float *red = scratch + 16;
 
-  auto one_clip = [&](const int clip, auto first_c) {
+  auto one_clip = [&](const int clip, int st, auto first_c) {
   constexpr bool first = decltype(first_c)::value;
   PL.clip = clip;
   if constexpr (!first) lds_barrier();        // the previous clip's factor store / loss sums have consumed H, G and scratch
   // Every lane loads UNCONDITIONALLY from a clamped (always valid) address and selects afterwards: a load inside a divergent
   // branch makes the compiler wait for it (and for every older load) at the branch's end.
-  const int st = d.skel_type[clip];
+  // The targets depend on clip, t and j alone. The reference tables of THIS clip's skeleton type (st) follow behind layer 0's barrier.
   float lraw[3], rraw[9];
-  {
-    const float *pl = d.ref_rel_loc + ((size_t)st * ph::J + jc) * 3;
-    lraw[0] = pl[0], lraw[1] = pl[1], lraw[2] = pl[2];
-    const float *pr = d.ref_rel_rot + ((size_t)st * ph::J + jc) * 9;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) rraw[i] = K::SCAN ? pr[i] : 0.f;
-  }
   float g2raw[2], g3raw[3];
   {
     const size_t frame = (size_t)clip * T + tc;
@@ -249,10 +283,10 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   }
   // ---- LinearAE forward of the clip's frames (mlp_fwd_kernel's first-tile schedule); the last layer writes y^T to LDS ----
   TT(0, 1);
-  tile_commit(S::dims(0), true, xr, H + S::h_off(0) * TP);
+  tile_commit<NTH>(S::dims(0), true, xr, H + S::h_off(0) * TP);
   {   // the next clip of this workgroup: its x tile waits in registers (rows beyond the batch read as zero, nothing is loaded)
     const int64_t nxt = (int64_t)clip + gridDim.x;
-    tile_issue(m.x, nxt * T, nxt < d.B ? nxt * T + T : 0, S::dims(0), true, xr);
+    tile_issue<NTH>(m.x, nxt * T, nxt < d.B ? nxt * T + T : 0, S::dims(0), true, xr);
   }
   // Layers 1 and 2 (13 and 6 outputs) are one output tile each, both on wave 0: they run back to back behind ONE workgroup
   // barrier, with a wave-local sync in between; layer 3's barrier publishes the rows of both. On the first clip the image
@@ -276,6 +310,14 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
     TT(0, 2 + ll);
     if constexpr (first) stage_issue(m.w_image, total4, wr, 0, issue_mark<S>(ll + 1), issue_mark<S>(ll + 2));
 #endif
+    if (ll == 0) {   // the skeleton type arrived with the x tile: the table loads go out with no wait of their own, far ahead of the pose phase
+      asm volatile("" : "+v"(st));            // (keeps the address arithmetic and the loads behind the barrier)
+      gcfloat *pl = (gcfloat *)ref_loc_lane + (size_t)st * (ph::J * 3);
+      lraw[0] = pl[0], lraw[1] = pl[1], lraw[2] = pl[2];
+      gcfloat *pr = (gcfloat *)ref_rot_lane + (size_t)st * (ph::J * 9);
+#pragma unroll
+      for (int i = 0; i < 9; ++i) rraw[i] = K::SCAN ? pr[i] : 0.f;
+    }
     const bool last = (ll == nl - 1);
     layer_forward<P2C_PREC_F32, true>(L, lds + S::w_off(ll), S::ld(ll), S::dims(ll), S::dims(ll + 1), !last, H + S::h_off(ll) * TP,
                   last ? Y : H + S::h_off(ll + 1) * TP, nullptr, false, false);
@@ -432,8 +474,9 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   TT(0, 39);
   };   // one_clip
 
-  if ((int)blockIdx.x < d.B) one_clip((int)blockIdx.x, std::true_type{});
-  for (int clip = (int)blockIdx.x + (int)gridDim.x; clip < d.B; clip += (int)gridDim.x) one_clip(clip, std::false_type{});
+  if ((int)blockIdx.x < d.B) one_clip((int)blockIdx.x, st_first, std::true_type{});
+  for (int clip = (int)blockIdx.x + (int)gridDim.x; clip < d.B; clip += (int)gridDim.x)
+    one_clip(clip, skel_type_of(clip), std::false_type{});   // (this clip's own type: nothing of it is carried across the loop)
 }
 
 // ---- second launch: weight gradient over all clips + optimizer + loss reduction ------------------------------------------
@@ -505,7 +548,25 @@ __global__ __launch_bounds__(64 * WG_WAVES) void train_wgrad_kernel(const WgradA
   __shared__ p2c_optim::Coefs sc;
   __shared__ int sc_ready;
   if (threadIdx.x == 0) sc_ready = 0;        // (published by the barrier behind the contraction)
-  if ((int)blockIdx.x == a.n_tiles_w * KS) {   // the loss reduction rides on this launch (256 of the 512 threads)
+  // Every kernel argument this workgroup will use is fetched HERE, in one batch under one wait, and pinned in registers. Fetched
+  // where it is used, each cost a scalar round trip of its own: the factors pointer one in front of the first factor load, the
+  // slices / counters pointers and the layer's gradient pointers (an array indexed at run time: re-read through memory at every
+  // use) ten more on wave 0's path from the contraction to its ticket.
+  typedef __attribute__((address_space(1))) float gfloat;
+  typedef __attribute__((address_space(1))) int32_t gint;
+  typedef __attribute__((address_space(1))) f32x4 gf32x4;
+  uintptr_t gW_[NLAY], gb_[NLAY];
+#pragma unroll
+  for (int i = 0; i < NLAY; ++i) gW_[i] = (uintptr_t)a.gW[i], gb_[i] = (uintptr_t)a.gb[i];
+  uintptr_t factors_p = (uintptr_t)a.factors, slices_p = (uintptr_t)a.slices, counters_p = (uintptr_t)a.counters;
+  uintptr_t o_step = (uintptr_t)o.step, o_grad = (uintptr_t)o.grad, o_param = (uintptr_t)o.param, o_m = (uintptr_t)o.exp_avg,
+            o_v = (uintptr_t)o.exp_avg_sq;
+  int n_tiles_w = a.n_tiles_w, n_stiles = a.n_stiles;
+#pragma unroll
+  for (int i = 0; i < NLAY; ++i) asm volatile("" : "+s"(gW_[i]), "+s"(gb_[i]));
+  asm volatile("" : "+s"(factors_p), "+s"(slices_p), "+s"(counters_p), "+s"(n_tiles_w), "+s"(n_stiles));
+  asm volatile("" : "+s"(o_step), "+s"(o_grad), "+s"(o_param), "+s"(o_m), "+s"(o_v));
+  if ((int)blockIdx.x == n_tiles_w * KS) {   // the loss reduction rides on this launch (256 of the 512 threads)
     __shared__ double fin[3][256];
     if (threadIdx.x >= 256) return;            // whole waves leave: the barriers below count the remaining four
     finalize_losses(a, fin);
@@ -516,33 +577,36 @@ __global__ __launch_bounds__(64 * WG_WAVES) void train_wgrad_kernel(const WgradA
   const int lane = threadIdx.x & 63, r = lane & 15, k = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int q = blockIdx.x % KS, t = blockIdx.x / KS;
-  int32_t dd[NLAY + 1];
-#pragma unroll
-  for (int i = 0; i <= NLAY; ++i) dd[i] = S::dim_at(i);
-  const TileRef tr = locate_tile(dd, t);
-  const int n_in = dd[tr.l], n_out = dd[tr.l + 1];
+  // The step count, read at kernel start: before any workgroup can publish the new one (the last tile does so only after every
+  // ticket is drawn, and this load has returned before its wave reaches the barrier below: a wave's loads retire in order and
+  // the contraction waits for the factor loads issued behind it). On the VECTOR path: the word was written by another CU at the
+  // end of the previous step, and a scalar read of it would sit under the first kernel-argument wait, a cache-missing round trip
+  // in front of the first factor load. This one travels beside the factor loads.
+  float step_prev = 0.f;
+  if (ADAM) step_prev = __hip_atomic_load((gfloat *)o_step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const StaticTile tr = locate_tile_static(t);
+  const int n_in = tr.n_in, n_out = tr.n_out;
   const int n = tr.ntile * 16 + r, mm = tr.mtile * 16 + r;
   const bool a_ok = n < n_out, b_ok = mm < n_in, b_one = mm == n_in;
-  int g_row = F_HALF, h_row = 0;                               // first factor row of G_{l+1} / H_l
-  for (int i = 1; i <= tr.l; ++i) g_row += dd[i];
-  for (int i = 0; i < tr.l; ++i) h_row += dd[i];
-  const size_t a_off = (size_t)(g_row + n) * 16 + 4 * k, b_off = (size_t)(h_row + mm) * 16 + 4 * k;
+  const size_t a_off = (size_t)(tr.g_row + n) * 16 + 4 * k, b_off = (size_t)(tr.h_row + mm) * 16 + 4 * k;
   const size_t f_tile = (size_t)F_ROWS * 16;
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f}, ones = {1.f, 1.f, 1.f, 1.f};
-  float step = 0.f;
-  if (ADAM) step = *o.step + 1.f;            // read at kernel start: before any workgroup can publish the new count
+  uintptr_t gW_l = gW_[0], gb_l = gb_[0];         // the tile's layer, by selects
+#pragma unroll
+  for (int i = 1; i < NLAY; ++i) gW_l = (i == tr.l) ? gW_[i] : gW_l, gb_l = (i == tr.l) ? gb_[i] : gb_l;
+  const gfloat *const factors = (const gfloat *)factors_p;
 
   auto load_a = [&](int st) -> f32x4 {
-    return a_ok ? *reinterpret_cast<const f32x4 *>(a.factors + (size_t)st * f_tile + a_off) : zero;
+    return a_ok ? *reinterpret_cast<const gf32x4 *>(factors + (size_t)st * f_tile + a_off) : zero;
   };
   auto load_b = [&](int st) -> f32x4 {
-    return b_one ? ones : (b_ok ? *reinterpret_cast<const f32x4 *>(a.factors + (size_t)st * f_tile + b_off) : zero);
+    return b_one ? ones : (b_ok ? *reinterpret_cast<const gf32x4 *>(factors + (size_t)st * f_tile + b_off) : zero);
   };
   f32x4 acc = zero;
   constexpr int UNROLL = 4;
   const int stride = KS * WG_WAVES;
   int st = q + KS * wave;
-  for (; st + (UNROLL - 1) * stride < a.n_stiles; st += UNROLL * stride) {   // UNROLL clips in flight
+  for (; st + (UNROLL - 1) * stride < n_stiles; st += UNROLL * stride) {   // UNROLL clips in flight
     f32x4 av[UNROLL], bv[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) av[u] = load_a(st + u * stride), bv[u] = load_b(st + u * stride);
@@ -552,17 +616,20 @@ __global__ __launch_bounds__(64 * WG_WAVES) void train_wgrad_kernel(const WgradA
       for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u][i], bv[u][i], acc, 0, 0, 0);
     }
   }
-  for (; st < a.n_stiles; st += stride) {
+  for (; st < n_stiles; st += stride) {
     const f32x4 av = load_a(st), bv = load_b(st);
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[i], acc, 0, 0, 0);
   }
   TB(1);
   red[wave][lane] = acc;
+  // a wave that had no clip to contract has waited for nothing yet: its read of the step count returns HERE, in front of the
+  // barrier and so in front of this workgroup's ticket (for every other wave it retired under the loop's waits: no cost)
+  if (ADAM) asm volatile("" ::"v"(step_prev));
   __syncthreads();
   if (wave == 1 && ADAM) {                   // the fp64 bias corrections of this step: off wave 0's critical path
     if (lane == 0) {
-      sc = p2c_optim::coefs(o, step);
+      sc = p2c_optim::coefs(o, step_prev + 1.f);
       __hip_atomic_store(&sc_ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     return;
@@ -574,26 +641,26 @@ __global__ __launch_bounds__(64 * WG_WAVES) void train_wgrad_kernel(const WgradA
   // what only the tile's last arriver will need is requested now by every slice (a few KB of L2 hits each): the latency
   // hides behind the publish / ticket round trips. Nobody else writes these words during this launch.
   const int m = tr.mtile * 16 + (lane & 15);
-  float *gp[4];
+  gfloat *gp[4];
   float pv[4], mv[4], vv[4];
 #pragma unroll
   for (int rr = 0; rr < 4; ++rr) {
     const int nn = tr.ntile * 16 + 4 * (lane >> 4) + rr;
-    gp[rr] = (nn < n_out && m <= n_in) ? ((m < n_in) ? a.gW[tr.l] + nn * n_in + m : a.gb[tr.l] + nn) : nullptr;
+    gp[rr] = (nn < n_out && m <= n_in) ? ((m < n_in) ? (gfloat *)gW_l + nn * n_in + m : (gfloat *)gb_l + nn) : nullptr;
     pv[rr] = mv[rr] = vv[rr] = 0.f;
     if (ADAM && gp[rr]) {
-      const ptrdiff_t off = gp[rr] - o.grad;
-      pv[rr] = o.param[off], mv[rr] = o.exp_avg[off], vv[rr] = o.exp_avg_sq[off];
+      const ptrdiff_t off = gp[rr] - (gfloat *)o_grad;
+      pv[rr] = ((gfloat *)o_param)[off], mv[rr] = ((gfloat *)o_m)[off], vv[rr] = ((gfloat *)o_v)[off];
     }
   }
   // ---- publish this slice's partial tile (16-byte write-through stores), draw the tile's ticket ----
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.slices, 0, KS * a.n_tiles_w * 1024, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((gfloat *)slices_p, 0, KS * n_tiles_w * 1024, 0x00020000);
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const int my_off = (q * a.n_tiles_w + t) * 1024 + lane * 16;
+  const int my_off = (q * n_tiles_w + t) * 1024 + lane * 16;
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, s), rs, my_off, 0, 16);      // aux 16 = sc1
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // the storing wave drains before it signals
   int ticket = 0;
-  if (lane == 0) ticket = __hip_atomic_fetch_add(a.counters + t, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (lane == 0) ticket = __hip_atomic_fetch_add((gint *)counters_p + t, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   ticket = __builtin_amdgcn_readfirstlane(ticket);                 // (the returned value is used: the add has completed)
   TB(2);
   if (ticket != KS - 1) return;
@@ -601,7 +668,7 @@ __global__ __launch_bounds__(64 * WG_WAVES) void train_wgrad_kernel(const WgradA
   f32x4 v[KS];
 #pragma unroll
   for (int qq = 0; qq < KS; ++qq)                                  // sc1 loads: past this CU's L1
-    v[qq] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (qq * a.n_tiles_w + t) * 1024 + lane * 16, 0, 16));
+    v[qq] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (qq * n_tiles_w + t) * 1024 + lane * 16, 0, 16));
   s = v[0];
 #pragma unroll
   for (int qq = 1; qq < KS; ++qq) s += v[qq];
@@ -616,19 +683,19 @@ __global__ __launch_bounds__(64 * WG_WAVES) void train_wgrad_kernel(const WgradA
     if (!gp[rr]) continue;
     *gp[rr] = (ADAM && o.zero_grad) ? 0.f : s[rr];   // zero_grad: the optimizer leaves the gradient buffer zeroed
     if (ADAM) {
-      const ptrdiff_t off = gp[rr] - o.grad;
+      const ptrdiff_t off = gp[rr] - (gfloat *)o_grad;
       if (o.adamw) p2c_optim::update<true>(c, pv[rr], s[rr], mv[rr], vv[rr]);
       else p2c_optim::update<false>(c, pv[rr], s[rr], mv[rr], vv[rr]);
-      o.param[off] = pv[rr], o.exp_avg[off] = mv[rr], o.exp_avg_sq[off] = vv[rr];
+      ((gfloat *)o_param)[off] = pv[rr], ((gfloat *)o_m)[off] = mv[rr], ((gfloat *)o_v)[off] = vv[rr];
       const int nn = tr.ntile * 16 + 4 * (lane >> 4) + rr;
       if (a.w_image) a.w_image[image_w_off(tr.l) + nn * image_ld(tr.l) + m] = pv[rr];    // bias sits in column n_in == m
     }
   }
   TB(4);
   if (lane == 0) {
-    __hip_atomic_store(a.counters + t, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed for the next launch
-    if (ADAM && atomicAdd(o.ticket, 1) == a.n_tiles_w - 1) {   // the last tile to finish publishes the new step count
-      *o.step = step;
+    __hip_atomic_store((gint *)counters_p + t, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed for the next launch
+    if (ADAM && atomicAdd(o.ticket, 1) == n_tiles_w - 1) {   // the last tile to finish publishes the new step count
+      *(gfloat *)o_step = step_prev + 1.f;
       *o.ticket = 0;
     }
   }
