@@ -135,9 +135,27 @@ __device__ __forceinline__ float group_max(float v) {
   for (int d = 16; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
   return v;
 }
+// Sum over the 64 lanes, in every lane: the xor butterfly 32, 16, 8, 4, 2, 1 (lane i adds the value of lane i ^ d), with the
+// partner's value moved by the VALU (gfx950 v_permlane32_swap / v_permlane16_swap, then DPP inside the 16-lane rows) and not by
+// ds_bpermute_b32: six LDS-crossbar trips, each waited for, were a dependent chain of their own. Same partners, same order;
+// a + b == b + a bit for bit, so every lane holds the bits the __shfl_xor loop gave it.
 __device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  {   // d = 32: swap(a, b) exchanges a's upper half with b's lower half -> (lo, lo) and (hi, hi)
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+  }
+  {   // d = 16: swap(a, b) exchanges a's odd rows with b's even rows -> (r0, r0, r2, r2) and (r1, r1, r3, r3)
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+  }
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xF, 0xF, false));   // row_ror:8 = lane ^ 8
+  {   // d = 4: lanes with bit 2 clear (banks 0, 2) take lane + 4 (row_shl:4), the others lane - 4 (row_shr:4)
+    int p = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x104, 0xF, 0x5, false);
+    p = __builtin_amdgcn_update_dpp(p, __float_as_int(v), 0x114, 0xF, 0xA, false);
+    v += __int_as_float(p);
+  }
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));    // quad_perm [2,3,0,1] = lane ^ 2
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));    // quad_perm [1,0,3,2] = lane ^ 1
   return v;
 }
 
@@ -283,8 +301,9 @@ struct HeadAcc {
 
 enum { MODE_FWD = 0, MODE_FWD_MATERIALIZE = 1, MODE_BWD = 2, MODE_TRAIN = 3 };   // TRAIN = BWD that also sums the losses
 
-template <int MODE>
-__device__ __forceinline__ V3 frame_head(const p2c_pose_head_desc &d, const LaneCtx &L, int t, V3 x, const World &W,
+// D: p2c_pose_head_desc, or a caller's own copy of the fields read here (train_clip_kernel: PoseConsts, fetched in one batch).
+template <int MODE, class D>
+__device__ __forceinline__ V3 frame_head(const D &d, const LaneCtx &L, int t, V3 x, const World &W,
                                          HeadAcc &acc, float coef2, float coef3, const float *g_abs_ext,
                                          const float *g_projt_ext, const float *gt2v, const float *gt3v) {
   constexpr bool BWD = (MODE == MODE_BWD || MODE == MODE_TRAIN);
@@ -302,7 +321,7 @@ __device__ __forceinline__ V3 frame_head(const p2c_pose_head_desc &d, const Lane
   float v = d.cam_cy + d.cam_f * (p.z + d.cam_elev) * invZ;
   if (!L.active) { u = 0.f; v = 0.f; invZ = 0.f; }
 
-  if (MAT) {
+  if constexpr (MAT) {
     if (L.active && d.out_projection_2d) {
       float *o = d.out_projection_2d + (frame * J + L.j) * 3;
       o[0] = u, o[1] = v, o[2] = invZ;
@@ -379,14 +398,16 @@ __device__ __forceinline__ V3 frame_head(const p2c_pose_head_desc &d, const Lane
     keep = wch >= d.near_zero;  // :35-37 third channel (1/depth) acts as the confidence
     if (!keep) { nu = 0.f; nv = 0.f; }
   }
-  if (MAT && tr != P2C_TRANSFORM_NONE && in_slice && L.clip < d.B) {
-    if (L.active && d.out_projection_2d_transformed) {
-      float *o = d.out_projection_2d_transformed + (frame * J + L.j) * 3;
-      o[0] = nu, o[1] = nv, o[2] = wch;
-    }
-    if (L.j == 0) {
-      if (d.out_shift) d.out_shift[frame * 2 + 0] = su, d.out_shift[frame * 2 + 1] = sv;
-      if (d.out_scale) d.out_scale[frame] = scale;
+  if constexpr (MAT) {
+    if (tr != P2C_TRANSFORM_NONE && in_slice && L.clip < d.B) {
+      if (L.active && d.out_projection_2d_transformed) {
+        float *o = d.out_projection_2d_transformed + (frame * J + L.j) * 3;
+        o[0] = nu, o[1] = nv, o[2] = wch;
+      }
+      if (L.j == 0) {
+        if (d.out_shift) d.out_shift[frame * 2 + 0] = su, d.out_shift[frame * 2 + 1] = sv;
+        if (d.out_scale) d.out_scale[frame] = scale;
+      }
     }
   }
 
@@ -493,7 +514,8 @@ __device__ __forceinline__ V3 frame_head(const p2c_pose_head_desc &d, const Lane
 }
 
 // world transform scan step (utils/world.py:16-63): rot[t] = rot[t-1] @ drot[t], loc[t] = loc[t-1] + dloc[t]
-__device__ __forceinline__ void world_step(const p2c_pose_head_desc &d, const LaneCtx &L, int t, World &W) {
+template <class D>
+__device__ __forceinline__ void world_step(const D &d, const LaneCtx &L, int t, World &W) {
   if (!W.on || L.clip >= d.B) return;
   size_t frame = (size_t)L.clip * d.T + t;
   if (d.drot) {
@@ -695,7 +717,8 @@ __device__ __forceinline__ void store_m3(float *base, size_t idx, const M3 &a) {
 }
 
 
-__device__ __forceinline__ World world_at(const p2c_pose_head_desc &d, const LaneCtx &L, int t) {
+template <class D>
+__device__ __forceinline__ World world_at(const D &d, const LaneCtx &L, int t) {
   World W;
   W.on = (d.dloc != nullptr) || (d.drot != nullptr);
   W.rot = identity();

@@ -126,6 +126,17 @@ __device__ __forceinline__ StaticTile locate_tile_static(int t) {
   }
   return r;
 }
+// The descriptor fields the pose phase reads (ph::world_at, ph::frame_head<MODE_TRAIN>): train_clip_kernel fetches them in ONE batch
+// behind the last forward layer's barrier -- the MLP's SGPR pressure is gone there and the fetch is in flight under that layer's MFMA
+// chain -- and keeps them in SGPRs. Read where they are used, each was a scalar load with a wait of its own inside the FK /
+// projection / normaliser chain (about fifteen on the executed path, the hips and neck indices twice). Fetched at the top of the
+// pose phase instead, the one wait stood in front of the y reads and gave back what the batch had won (profiles/k13_tail).
+struct PoseConsts {
+  typedef __attribute__((address_space(1))) const float gcfloat;
+  int32_t B, T, t0, t1, transform, n_hips, n_neck, hips_idx[2], neck_idx[2], mask_missing_joints, world_absolute;
+  float near_zero, cam_f, cam_cx, cam_cy, cam_dist, cam_elev;
+  gcfloat *dloc, *drot;
+};
 // inclusive scan over the frames of the clip, P_t = c_t c_{t-1} ... c_0 (the order of p2c::scan_time), ping-pong planes
 __device__ __forceinline__ ph::M3 scan_time2(ph::M3 P, int t, int j, int T, float *p0, float *p1) {
   float *cur = p0, *oth = p1;
@@ -259,10 +270,47 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   // pair counts: issued now, consumed after the first clip's MLP forward (no add here: an add would wait for every load above)
   const float c0raw = m.counts[(int)threadIdx.x < d.B ? threadIdx.x : 0];
   const float c1raw = m.counts[(int)threadIdx.x + NTH < d.B ? threadIdx.x + NTH : 0];
+  // upstream gradients of the three losses (device scalars, any of them may be null): asked for here, from always-valid
+  // addresses, and selected where the loss coefficients are formed. Pointers pinned in VGPRs: vector loads beside the others.
+  float uraw[3];
+  {
+    uintptr_t up[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) up[i] = (uintptr_t)(gl.p[i] ? gl.p[i] : m.counts);
+    asm volatile("" : "+v"(up[0]), "+v"(up[1]), "+v"(up[2]));
+#pragma unroll
+    for (int i = 0; i < 3; ++i) uraw[i] = *(gcfloat *)up[i];
+  }
   if (blockIdx.x == 0 && (int)threadIdx.x < m.n_counters) m.counters[threadIdx.x] = 0;   // arrival tickets of train_wgrad_kernel
   init_rows<NTH>(H, S::h_off(0) + S::dims(0), S::h_off(0) + k_rows(S::dims(0)), S::h_off(0) + S::dims(0));
-  float coef2 = 0.f, coef3 = 0.f;             // loss coefficients: the same for every clip, worked out in the first one
+  // Loss coefficients: the same for every clip of the launch. In the workgroup's first clip every thread leaves the two pair counts
+  // it loaded in the scan plane (dead during the forward), as they came, in front of layer 1's barrier: two LDS stores on wave 0's
+  // path. Wave 1, idle while wave 0 runs layers 1 -> 2, drops the entries beyond the batch, adds the rest (small integers held in
+  // floats: exact in any order), does the two divisions (= ph::loss_coefs_n) and leaves the results in scratch[0..1], which layer 3's
+  // barrier publishes.
+  float coef2 = 0.f, coef3 = 0.f;
   float *red = scratch + 16;
+  static_assert(WAVES >= 2 && 16 + 3 * WAVES <= SCRATCH && 2 * NTH <= PLANE, "scratch: coefficients, loss sums; plane 0: pair counts");
+
+  auto clip_pair_count = [&]() { plane0[threadIdx.x] = c0raw, plane0[threadIdx.x + NTH] = c1raw; };
+  auto clip_loss_coefs = [&]() {
+    float n2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 2 * NTH / 64; ++k) {
+      const float c = plane0[L.lane + 64 * k];
+      n2 += L.lane + 64 * k < d.B ? c : 0.f;
+    }
+    for (int i = L.lane + 2 * NTH; i < d.B; i += 64) n2 += m.counts[i];
+    n2 = ph::wave_sum(n2);
+    float k2 = 0.f, k3 = 0.f;
+    if (gl.p[0] || gl.p[1] || gl.p[2]) {
+      const float u0 = gl.p[0] ? uraw[0] : 0.f, u1 = gl.p[1] ? uraw[1] : 0.f, u2 = gl.p[2] ? uraw[2] : 0.f;
+      const float g2 = u0 + u2, g3 = u1 + u2, n3 = m.n3_elems;
+      k2 = (d.gt2d && n2 > 0.f) ? g2 / n2 : 0.f;
+      k3 = (d.gt3d && n3 > 0.f) ? 2.f * g3 / n3 : 0.f;
+    }
+    if (L.lane == 0) scratch[0] = k2, scratch[1] = k3;
+  };
 
   auto one_clip = [&](const int clip, int st, auto first_c) {
   constexpr bool first = decltype(first_c)::value;
@@ -293,10 +341,14 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   // rounds of layer 2 are therefore committed in front of layer 1's barrier.
   static_assert(S::dims(2) + 1 <= 16 && S::dims(3) + 1 <= 16, "layers 1 and 2: one output tile each");
   static_assert(rounds_upto<S>(2) <= issue_mark<S>(2), "layer 2's image rounds are in flight before layer 1's barrier commits them");
+  PoseConsts pc;
   for_layers(sh, 0, nl, [&](int ll) {
     const bool run = ll == 2;           // second layer of the single-wave run: no workgroup barrier
 #if P2C_TRAIN_DMA_IMAGE
     if constexpr (first) image_dma_wait(ll == 1 ? 2 : ll, L.wave);
+    if constexpr (first) {
+      if (ll == 1) clip_pair_count();
+    }
     if (run) lds_wave_sync();
     else lds_barrier();
     TT(0, 2 + ll);
@@ -305,11 +357,17 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
       const int upto = ll == 1 ? 2 : ll;
       if (!run) stage_commit(total4, wr, lds, 0, ll == 0 ? 0 : rounds_upto<S>(ll - 1), rounds_upto<S>(upto));
     }
+    if constexpr (first) {
+      if (ll == 1) clip_pair_count();
+    }
     if (run) lds_wave_sync();
     else lds_barrier();
     TT(0, 2 + ll);
     if constexpr (first) stage_issue(m.w_image, total4, wr, 0, issue_mark<S>(ll + 1), issue_mark<S>(ll + 2));
 #endif
+    if constexpr (first) {
+      if (ll == 2 && L.wave == 1) clip_loss_coefs();
+    }
     if (ll == 0) {   // the skeleton type arrived with the x tile: the table loads go out with no wait of their own, far ahead of the pose phase
       asm volatile("" : "+v"(st));            // (keeps the address arithmetic and the loads behind the barrier)
       gcfloat *pl = (gcfloat *)ref_loc_lane + (size_t)st * (ph::J * 3);
@@ -319,6 +377,15 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
       for (int i = 0; i < 9; ++i) rraw[i] = K::SCAN ? pr[i] : 0.f;
     }
     const bool last = (ll == nl - 1);
+    if (last) {   // the pose phase's descriptor fields: one batch, in flight under the last layer's MFMA chain
+      pc = PoseConsts{d.B, d.T, d.t0, d.t1, d.transform, d.n_hips, d.n_neck, {d.hips_idx[0], d.hips_idx[1]}, {d.neck_idx[0], d.neck_idx[1]},
+                    d.mask_missing_joints, d.world_absolute, d.near_zero, d.cam_f, d.cam_cx, d.cam_cy, d.cam_dist, d.cam_elev,
+                    (PoseConsts::gcfloat *)d.dloc, (PoseConsts::gcfloat *)d.drot};
+      asm volatile("" : "+s"(pc.B), "+s"(pc.T), "+s"(pc.t0), "+s"(pc.t1), "+s"(pc.transform), "+s"(pc.n_hips), "+s"(pc.n_neck),
+                   "+s"(pc.hips_idx[0]), "+s"(pc.hips_idx[1]), "+s"(pc.neck_idx[0]), "+s"(pc.neck_idx[1]), "+s"(pc.mask_missing_joints));
+      asm volatile("" : "+s"(pc.world_absolute), "+s"(pc.near_zero), "+s"(pc.cam_f), "+s"(pc.cam_cx), "+s"(pc.cam_cy), "+s"(pc.cam_dist),
+                   "+s"(pc.cam_elev), "+s"(pc.dloc), "+s"(pc.drot));
+    }
     layer_forward<P2C_PREC_F32, true>(L, lds + S::w_off(ll), S::ld(ll), S::dims(ll), S::dims(ll + 1), !last, H + S::h_off(ll) * TP,
                   last ? Y : H + S::h_off(ll + 1) * TP, nullptr, false, false);
   });
@@ -339,31 +406,19 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   }
   const float g2[2] = {PL.has2 ? g2raw[0] : 0.f, PL.has2 ? g2raw[1] : 0.f};
   const float g3[3] = {PL.has3 ? g3raw[0] : 0.f, PL.has3 ? g3raw[1] : 0.f, PL.has3 ? g3raw[2] : 0.f};
-  if constexpr (first) {
-    const float c0 = (int)threadIdx.x < d.B ? c0raw : 0.f, c1 = (int)threadIdx.x + NTH < d.B ? c1raw : 0.f;
-    float cnt = c0 + c1;                      // small integers held in floats: exact in any order
-    for (int i = threadIdx.x + 2 * NTH; i < d.B; i += NTH) cnt += m.counts[i];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    if (L.lane == 0) scratch[L.wave] = cnt;
-  }
+  if constexpr (first) coef2 = scratch[0], coef3 = scratch[1];   // (wave 1 left them during layers 1 -> 2)
   ph::SixD s;
   const ph::M3 c = ph::rot6d_fwd(y6, s);
   ph::M3 R = c;
-  if (K::SCAN) R = ph::mul(scan_time2(c, t, PL.j, T, plane0, plane1), Rref);     // (its barriers also publish scratch[])
+  if (K::SCAN) R = ph::mul(scan_time2(c, t, PL.j, T, plane0, plane1), Rref);
   else lds_barrier();
   TT(0, 9);
-  if constexpr (first) {
-    float n2 = 0.f;
-    for (int w = 0; w < WAVES; ++w) n2 += scratch[w];
-    ph::loss_coefs_n(d, gl, n2, ph::n3_elems(d), coef2, coef3);
-  }
   ph::M3 A = R;
   ph::V3 x = l;
   ph::fk_doubling(PL, A, x);
-  const ph::World W = ph::world_at(d, PL, t);
+  const ph::World W = ph::world_at(pc, PL, t);
   ph::HeadAcc acc{0.f, 0.f, 0.f};
-  ph::V3 F = ph::frame_head<ph::MODE_TRAIN>(d, PL, t, x, W, acc, coef2, coef3, nullptr, nullptr, g2, g3);
+  ph::V3 F = ph::frame_head<ph::MODE_TRAIN>(pc, PL, t, x, W, acc, coef2, coef3, nullptr, nullptr, g2, g3);
   TT(0, 10);
   {   // this clip's loss sums: per wave now, added in frame order at the very end (the barriers below publish red[])
     const float s2 = ph::wave_sum(acc.sum2), c2 = ph::wave_sum(acc.cnt2), s3 = ph::wave_sum(acc.sum3);
@@ -452,24 +507,47 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
     layer_dgrad<P2C_PREC_F32, true>(L, lds + S::w_off(ll), S::ld(ll), S::dims(ll), S::dims(ll + 1), G + S::h_off(ll + 1) * TP, H + S::h_off(ll) * TP,
                 G + S::h_off(ll) * TP);
   });
+  // the clip's slot of the loss partials: the descriptor field is fetched under this barrier's wait, not behind wave 0's last store
+  uintptr_t part_p = (uintptr_t)(d.partials + (size_t)clip * 4);
+  asm volatile("" : "+s"(part_p));
   lds_barrier();
   TT(0, 20);
 
   // ---- the clip's factors, as they sit in LDS (transposed, 16 samples = 64 B per row) ----
   f32x4 *fdst = reinterpret_cast<f32x4 *>(m.factors) + (size_t)clip * F_ROWS * 4;
-  auto put = [&](const float *src, f32x4 *dst, int rows) {
-    for (int i = threadIdx.x; i < rows * 4; i += NTH) {
-      const int o = (i >> 2) * TP + (i & 3) * 4;
-      dst[i] = (f32x4){src[o], src[o + 1], src[o + 2], src[o + 3]};
-    }
-  };
-  for_layers(sh, 0, nl, [&](int ll) { put(H + S::h_off(ll) * TP, fdst + f_h_off(ll) * 4, S::dims(ll)); });
-  for_layers(sh, 0, nl, [&](int ll) { put(G + S::h_off(ll + 1) * TP, fdst + f_g_off(ll + 1) * 4, S::dims(ll + 1)); });
-  if (threadIdx.x == 0) {
+  // One batch: every LDS read of the thread first (item i = this thread's k-th sixteen bytes of the dense block, taken from the
+  // padded row that holds factor row i / 4), then the stores back to back. Twelve per-segment loops were thirteen dependent rounds of
+  // address arithmetic, LDS read, wait, store and a mask branch; the block is contiguous in memory, so five rounds cover it.
+  // The loss partials of the clip ride along: wave 0 reads the 24 per-wave sums in the same LDS trip and adds them in wave order
+  // once its stores are out.
+  constexpr int F_ITEMS = F_ROWS * 4, F_ROUNDS = (F_ITEMS + NTH - 1) / NTH;
+  f32x4 fv[F_ROUNDS];
+#pragma unroll
+  for (int k = 0; k < F_ROUNDS; ++k) {
+    int i = threadIdx.x + k * NTH;
+    if ((k + 1) * NTH > F_ITEMS) i = i < F_ITEMS ? i : F_ITEMS - 1;       // (the last round is partial: read a valid row, store nothing)
+    const int hi = ((k + 1) * NTH - 1) >> 2;
+    const int o = f_lds_row(i >> 2, (k * NTH) >> 2, hi < F_ROWS ? hi : F_ROWS - 1) * TP + (i & 3) * 4;
+    fv[k] = (f32x4){H[o], H[o + 1], H[o + 2], H[o + 3]};
+  }
+  float rv[3 * WAVES];
+  if (L.wave == 0) {
+#pragma unroll
+    for (int i = 0; i < 3 * WAVES; ++i) rv[i] = red[i];
+  }
+#pragma unroll
+  for (int k = 0; k < F_ROUNDS; ++k) {
+    const int i = threadIdx.x + k * NTH;
+    if ((k + 1) * NTH <= F_ITEMS || i < F_ITEMS) fdst[i] = fv[k];
+  }
+  if (L.wave == 0) {
     float a = 0.f, b = 0.f, cc = 0.f;
-    for (int w = 0; w < WAVES; ++w) a += red[w * 3], b += red[w * 3 + 1], cc += red[w * 3 + 2];
-    float *pp = d.partials + (size_t)clip * 4;
-    pp[0] = a, pp[1] = b, pp[2] = cc, pp[3] = 0.f;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) a += rv[w * 3], b += rv[w * 3 + 1], cc += rv[w * 3 + 2];
+    if (L.lane == 0) {
+      __attribute__((address_space(1))) float *pp = (__attribute__((address_space(1))) float *)part_p;
+      pp[0] = a, pp[1] = b, pp[2] = cc, pp[3] = 0.f;
+    }
   }
   TT(0, 39);
   };   // one_clip
@@ -1101,7 +1179,8 @@ extern "C" int p2c_train_step_launch(const p2c_train_step_desc *desc, const floa
   int32_t *counters = reinterpret_cast<int32_t *>(slices + (size_t)WS_BLOCKS_MAX * kTilesW * 256);
   int identity = 1;
   for (int j = 0; j < P2C_JOINTS; ++j) identity &= (d.gmap2d[j] == j) && (d.gmap3d[j] == j);
-  ClipArgs ca{m.x, m.w_image, desc->pair_counts, m.partials, counters, tiles, identity};
+  const float n3_elems = (float)((double)d.B * (double)(d.t1 - d.t0) * (double)d.n_common3d * 3.0);   // = ph::n3_elems(d)
+  ClipArgs ca{m.x, m.w_image, desc->pair_counts, m.partials, counters, tiles, identity, n3_elems};
   const size_t lds_a = (size_t)LDS_FLOATS * sizeof(float);
   hipError_t e = hipSuccess;
   const dim3 grid_a((unsigned)(d.B < kClipBlocks ? d.B : kClipBlocks));   // persistent: one workgroup per CU walks its clips
@@ -1125,7 +1204,7 @@ extern "C" int p2c_train_step_launch(const p2c_train_step_desc *desc, const floa
   wa.w_image = adam ? m.w_image : nullptr;
   wa.slices = slices, wa.counters = counters;
   wa.loss_partials = d.partials;
-  wa.n3_elems = (float)((double)d.B * (double)(d.t1 - d.t0) * (double)d.n_common3d * 3.0);
+  wa.n3_elems = n3_elems;
   wa.has2d = d.gt2d ? 1 : 0, wa.has3d = d.gt3d ? 1 : 0;
   wa.loss_sums = d.loss_sums, wa.losses = d.losses;
   if (d.B >= wgrad_stream_min_b()) {

@@ -39,7 +39,26 @@ struct ClipArgs {
   int32_t *counters;       // arrival tickets of the second launch: zeroed here
   int32_t n_counters;
   int32_t identity_maps;   // gmap2d[j] == gmap3d[j] == j for every joint (host-checked)
+  float n3_elems;          // the loc_3d denominator B (t1 - t0) n_common3d 3 (= p2c::n3_elems, worked out on the host)
 };
+
+// Row of the activation area (counted from H_0's first row, pitch TP) that holds factor row r: the twelve segments H_0 .. H_{L-1},
+// G_1 .. G_L are dense in the factor block and padded in LDS. A caller that knows r lies in [lo, hi] pays one compare and select
+// per segment boundary inside that range; the boundaries are compile-time constants.
+__host__ __device__ constexpr int f_seg_start(int s) { return s < NLAY ? f_h_off(s) : f_g_off(s - NLAY + 1); }
+__host__ __device__ constexpr int f_seg_lds_row(int s) {
+  return s < NLAY ? S::h_off(s) : S::h_off(NLAY) - S::h_off(1) + S::h_off(s - NLAY + 1);
+}
+__device__ __forceinline__ int f_lds_row(int r, int lo, int hi) {
+  int shift = 0;
+#pragma unroll
+  for (int s = 1; s < 2 * NLAY; ++s) {
+    const int d = f_seg_lds_row(s) - f_seg_start(s);
+    if (f_seg_start(s) <= lo) shift = d;
+    else if (f_seg_start(s) <= hi) shift = r >= f_seg_start(s) ? d : shift;
+  }
+  return r + shift;
+}
 
 }  // namespace p2c_train
 
