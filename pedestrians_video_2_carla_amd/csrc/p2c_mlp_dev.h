@@ -384,6 +384,50 @@ __host__ __device__ constexpr int dgrad_ksteps(int n_out) {
   return (P == P2C_PREC_F32 && EXACT) ? ks : (ks + 3) & ~3;
 }
 
+// The fp32 chains of a shape known at compile time (EXACT): NT accumulators over `ksteps` k-steps, step k of tile h on operands
+// a_at(h, k) and b_at(k) (LDS reads), the MFMAs in the order k-major, h inner. The reads of step k + WEAVE_AHEAD stand in the gaps
+// behind the MFMAs of step k, one A and at most one B read per gap, not as a block of six to ten reads between two groups of
+// four MFMAs. A lone wave hides either form in the ~30 cycles it idles behind a dependent v_mfma_f32_16x16x4_f32 (35 cycles per
+// step both ways, tools/exp/mfmaweave.hip); where several waves of the CU run chains at once (layers 4 and 5) their read blocks
+// queue up at the LDS behind one another and the woven form is shorter: 7 % there, 13 - 19 % in dgrad steps 5 and 4 of the clip
+// kernel (profiles/k13_weave/). The operands live in a ring of eight steps (step k in slot k & 7: the slot a read fills was last
+// used by an MFMA at least 8 - WEAVE_AHEAD steps back); the last WEAVE_AHEAD steps issue no read, so nothing beyond step
+// ksteps - 1 is ever addressed. Fully unrolled: ksteps must be a constant once the caller is inlined. The sched_barriers pin
+// the reads into their gaps; the last WEAVE_AHEAD MFMAs have no read behind them and stay unfenced, so the caller's epilogue may
+// be scheduled into their shadow.
+#ifndef P2C_MLP_WEAVE_AHEAD
+#define P2C_MLP_WEAVE_AHEAD 4
+#endif
+constexpr int WEAVE_AHEAD = P2C_MLP_WEAVE_AHEAD;   // steps in flight in front of the first MFMA
+static_assert(WEAVE_AHEAD >= 1 && WEAVE_AHEAD <= 8, "the operand ring holds eight steps");
+template <int NT, class FA, class FB>
+__device__ __forceinline__ void woven_chain(f32x4 (&acc)[NT], int ksteps, FA &&a_at, FB &&b_at) {
+  float a[NT][8], b[8];
+#pragma unroll
+  for (int k = 0; k < WEAVE_AHEAD; ++k) {
+    if (k < ksteps) {
+      b[k] = b_at(k);
+#pragma unroll
+      for (int h = 0; h < NT; ++h) a[h][k] = a_at(h, k);
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int k = 0; k < ksteps; ++k) {
+    const int n = k + WEAVE_AHEAD;
+#pragma unroll
+    for (int h = 0; h < NT; ++h) {
+      acc[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[h][k & 7], b[k & 7], acc[h], 0, 0, 0);
+      if (n < ksteps) {
+        __builtin_amdgcn_sched_barrier(0);
+        a[h][n & 7] = a_at(h, n);
+        if (h == NT - 1) b[n & 7] = b_at(n);   // behind the step's last MFMA: with WEAVE_AHEAD == 8 it is the slot just read
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  }
+}
+
 // out^T[n][s] = act( sum_k Waug[n][k] in^T_aug[k][s] ) for NT output tiles of this wave (nt0, nt0 + WAVES)
 template <int NT, int STRIDE = WAVES, int P = P2C_PREC_F32, bool EXACT = false>
 __device__ __forceinline__ void layer_forward_nt(const Lane &L, const float *wl, int ld, int ksteps, int nt0, int n_out,
@@ -397,84 +441,45 @@ __device__ __forceinline__ void layer_forward_nt(const Lane &L, const float *wl,
     ap[h] = wl + ((nt0 + h * STRIDE) * 16 + L.c) * ld + L.g;
   }
   const float *bp = in + L.g * TP + L.c;
-  // Ping-pong software pipeline: the operands of k-group s+1 are in flight while the MFMAs of group s run. With EXACT ksteps >= 1
-  // is any count: whole groups of four steps, then a tail of 1..3 steps whose operands travel with the last whole group's MFMAs;
-  // otherwise it is a multiple of four and there is no tail.
-  // The sched_barriers keep the compiler from sinking the loads below the MFMAs they overlap.
-  float b0[4], a0[NT][4], b1[4], a1[NT][4];
-  [[maybe_unused]] const int full = ksteps & ~3, tail = ksteps & 3;
-  auto load = [&](float (&bv)[4], float (&av)[NT][4], int s, int n) {   // n: steps of this group (wave-uniform)
+  if constexpr (EXACT && P == P2C_PREC_F32) {   // ksteps >= 1 is any count; reads woven into the chains
+    woven_chain<NT>(acc, ksteps, [&](int h, int k) { return ap[h][k * 4]; }, [&](int k) { return bp[k * 4 * TP]; });
+  } else {
+    // Ping-pong software pipeline over whole groups of four steps (ksteps is a multiple of 4, >= 4): the operands of k-group s+1
+    // are in flight while the MFMAs of group s run.
+    // The sched_barriers keep the compiler from sinking the loads below the MFMAs they overlap.
+    float b0[4], a0[NT][4], b1[4], a1[NT][4];
+    auto load = [&](float (&bv)[4], float (&av)[NT][4], int s) {
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (u < n) {
+      for (int u = 0; u < 4; ++u) {
         bv[u] = bp[(s + u) * 4 * TP];
 #pragma unroll
         for (int h = 0; h < NT; ++h) av[h][u] = ap[h][(s + u) * 4];
       }
-    }
-  };
-  auto fma4 = [&](const float (&bv)[4], const float (&av)[NT][4]) {
-    if constexpr (P == P2C_PREC_F32) {
+    };
+    auto fma4 = [&](const float (&bv)[4], const float (&av)[NT][4]) {
+      if constexpr (P == P2C_PREC_F32) {
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-#pragma unroll
-        for (int h = 0; h < NT; ++h) acc[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[h][u], bv[u], acc[h], 0, 0, 0);
-      }
-    } else {
-#pragma unroll
-      for (int h = 0; h < NT; ++h) acc[h] = mfma_k16<P>(av[h], bv, acc[h]);
-    }
-  };
-  auto fma_tail = [&](const float (&bv)[4], const float (&av)[NT][4]) {   // fp32 only: the other forms have no tail
-    if constexpr (P == P2C_PREC_F32) {
-#pragma unroll
-      for (int u = 0; u < 3; ++u) {
-        if (u < tail) {
+        for (int u = 0; u < 4; ++u) {
 #pragma unroll
           for (int h = 0; h < NT; ++h) acc[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[h][u], bv[u], acc[h], 0, 0, 0);
         }
+      } else {
+#pragma unroll
+        for (int h = 0; h < NT; ++h) acc[h] = mfma_k16<P>(av[h], bv, acc[h]);
       }
-    }
-  };
-  if constexpr (!EXACT) {   // whole groups only (ksteps is a multiple of 4, >= 4)
-    load(b0, a0, 0, 4);
+    };
+    load(b0, a0, 0);
     for (int s = 4;; s += 8) {
-      if (s < ksteps) load(b1, a1, s, 4);
+      if (s < ksteps) load(b1, a1, s);
       __builtin_amdgcn_sched_barrier(0);
       fma4(b0, a0);
       __builtin_amdgcn_sched_barrier(0);
       if (s >= ksteps) break;
-      if (s + 4 < ksteps) load(b0, a0, s + 4, 4);
+      if (s + 4 < ksteps) load(b0, a0, s + 4);
       __builtin_amdgcn_sched_barrier(0);
       fma4(b1, a1);
       __builtin_amdgcn_sched_barrier(0);
       if (s + 4 >= ksteps) break;
-    }
-  } else if (full == 0) {
-    load(b0, a0, 0, tail);
-    __builtin_amdgcn_sched_barrier(0);
-    fma_tail(b0, a0);
-  } else {
-    load(b0, a0, 0, 4);
-    for (int s = 4;; s += 8) {
-      if (s < full) load(b1, a1, s, 4);
-      else load(b1, a1, s, tail);
-      __builtin_amdgcn_sched_barrier(0);
-      fma4(b0, a0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (s >= full) {
-        fma_tail(b1, a1);
-        break;
-      }
-      if (s + 4 < full) load(b0, a0, s + 4, 4);
-      else load(b0, a0, s + 4, tail);
-      __builtin_amdgcn_sched_barrier(0);
-      fma4(b1, a1);
-      __builtin_amdgcn_sched_barrier(0);
-      if (s + 4 >= full) {
-        fma_tail(b0, a0);
-        break;
-      }
     }
   }
 #pragma unroll
@@ -520,71 +525,38 @@ __device__ __forceinline__ void layer_dgrad(const Lane &L, const float *wl, int 
                                             const float *Hprev, float *gout) {
   const int ksteps = dgrad_ksteps<P, EXACT>(n_out);            // image rows and G rows are zero beyond n_out
   const int mtiles = (n_in + 15) >> 4;
-  [[maybe_unused]] const int full = ksteps & ~3, tail = ksteps & 3;
   for (int mt = L.wave; mt < mtiles; mt += WAVES) {
-    f32x4 c0 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 c0[1] = {{0.f, 0.f, 0.f, 0.f}};
     const float *a0p = wl + L.g * ld + mt * 16 + L.c;
     const float *bp = gin + L.g * TP + L.c;
-    float b0[4], a0[4], b1[4], a1[4];
-    auto load = [&](float (&bv)[4], float (&av)[4], int s, int n) {   // n: steps of this group (wave-uniform)
+    if constexpr (EXACT && P == P2C_PREC_F32) {   // any count of steps; reads woven into the chain
+      woven_chain<1>(c0, ksteps, [&](int, int k) { return a0p[k * 4 * ld]; }, [&](int k) { return bp[k * 4 * TP]; });
+    } else {   // whole groups only: the same ping-pong pipeline as layer_forward_nt
+      float b0[4], a0[4], b1[4], a1[4];
+      auto load = [&](float (&bv)[4], float (&av)[4], int s) {
 #pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (u < n) bv[u] = bp[(s + u) * 4 * TP], av[u] = a0p[(s + u) * 4 * ld];
-    };
-    auto fma4 = [&](const float (&bv)[4], const float (&av)[4]) { c0 = mfma_k16<P>(av, bv, c0); };
-    auto fma_tail = [&](const float (&bv)[4], const float (&av)[4]) {   // fp32 only: the other forms have no tail
-      if constexpr (P == P2C_PREC_F32) {
-#pragma unroll
-        for (int u = 0; u < 3; ++u)
-          if (u < tail) c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], c0, 0, 0, 0);
-      }
-    };
-    if constexpr (!EXACT) {   // whole groups only
-      load(b0, a0, 0, 4);
-      for (int s = 4;; s += 8) {   // same ping-pong pipeline as layer_forward_nt
-        if (s < ksteps) load(b1, a1, s, 4);
+        for (int u = 0; u < 4; ++u) bv[u] = bp[(s + u) * 4 * TP], av[u] = a0p[(s + u) * 4 * ld];
+      };
+      auto fma4 = [&](const float (&bv)[4], const float (&av)[4]) { c0[0] = mfma_k16<P>(av, bv, c0[0]); };
+      load(b0, a0, 0);
+      for (int s = 4;; s += 8) {
+        if (s < ksteps) load(b1, a1, s);
         __builtin_amdgcn_sched_barrier(0);
         fma4(b0, a0);
         __builtin_amdgcn_sched_barrier(0);
         if (s >= ksteps) break;
-        if (s + 4 < ksteps) load(b0, a0, s + 4, 4);
+        if (s + 4 < ksteps) load(b0, a0, s + 4);
         __builtin_amdgcn_sched_barrier(0);
         fma4(b1, a1);
         __builtin_amdgcn_sched_barrier(0);
         if (s + 4 >= ksteps) break;
-      }
-    } else if (full == 0) {
-      load(b0, a0, 0, tail);
-      __builtin_amdgcn_sched_barrier(0);
-      fma_tail(b0, a0);
-    } else {
-      load(b0, a0, 0, 4);
-      for (int s = 4;; s += 8) {
-        if (s < full) load(b1, a1, s, 4);
-        else load(b1, a1, s, tail);
-        __builtin_amdgcn_sched_barrier(0);
-        fma4(b0, a0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (s >= full) {
-          fma_tail(b1, a1);
-          break;
-        }
-        if (s + 4 < full) load(b0, a0, s + 4, 4);
-        else load(b0, a0, s + 4, tail);
-        __builtin_amdgcn_sched_barrier(0);
-        fma4(b1, a1);
-        __builtin_amdgcn_sched_barrier(0);
-        if (s + 4 >= full) {
-          fma_tail(b0, a0);
-          break;
-        }
       }
     }
     const int mb = mt * 16 + 4 * L.g;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float hv = Hprev[(mb + r) * TP + L.c];
-      gout[(mb + r) * TP + L.c] = (mb + r < n_in && hv > 0.f) ? c0[r] : 0.f;
+      gout[(mb + r) * TP + L.c] = (mb + r < n_in && hv > 0.f) ? c0[0][r] : 0.f;
     }
   }
 }
