@@ -975,6 +975,42 @@ P2C_API int p2c_carla_pose_fwd(const float *rel_loc, const float *rel_rot, const
 P2C_API int p2c_carla_pose_inv(const float *bones, float *loc, float *rot, int64_t N, int32_t J, int32_t max_blocks,
                                void *stream);
 
+/* ---- K32: keypoint clips -> CARLA bone transforms in one launch (csrc/p2c_lift.hip) -----------------------------------------
+ * For B clips of T frames: LinearAE.forward (the 52-26-13-6-39-78-156 model, p2c_mlp_fwd's arithmetic) -> the relative
+ * rotations of the materialising pose head (pose_head_rot_fwd<KIND, true>: c = rot6d(y_t), R = c R for pose_changes, R = c for
+ * relative_rot, frames in order) -> the rows of p2c_carla_pose_fwd with relative_pose_loc = ref_rel_loc[skel_type]. The model
+ * output and the rotations stay in LDS; no forward kinematics, no projection. One workgroup per clip, a clip in tiles of 16
+ * frames, any B >= 1 and T >= 1; the same bits as the three separate calls.
+ * mlp: x (B*T, 52), N = B*T, dims, w_image and skip_pack as for p2c_mlp_fwd (skip_pack == 0: W / b are read by one
+ *   p2c_mlp_pack launch first); precision P2C_PREC_F32; y / gy / gW / gb / partials / saved / fused_adamw unused.
+ * kind: P2C_KIND_POSE_CHANGES_6D or P2C_KIND_RELATIVE_ROT_6D (P2C_E_ENUM otherwise).
+ * world_loc (B,T,3) / world_rot (B,T,3,3): the world transform of each frame, both or neither; NULL = the identity world.
+ * initial_rel_rot (B,26,3,3) or NULL: where the running rotation starts instead of ref_rel_rot[skel_type] (pose_changes; a
+ *   video cut into clips hands the previous clip's final_rel_rot here).
+ * bones (B,T,26,6); root (B,T,6) or NULL; final_rel_rot (B,26,3,3) or NULL, written for the pose_changes kind only;
+ * out_relative_pose_rot (B,T,26,3,3) or NULL. Every output element has one writer, nothing is reduced, no workspace.
+ * max_blocks 0: one workgroup per CU at most; > 0 lowers that cap (workgroups stride over the clips).
+ * B == 0 or T == 0: nothing is launched. Negative sizes, a geometry p2c_lift_supported refuses: P2C_E_SHAPE; a missing
+ * tensor or one world input without the other: P2C_E_NULL; all before any launch. */
+typedef struct p2c_lift_desc {
+  p2c_mlp_desc mlp;
+  int32_t B, T;
+  int32_t kind;
+  int32_t max_blocks;
+  const int32_t *skel_type;        /* (B) in [0,4) */
+  const float *ref_rel_loc;        /* (4,26,3) */
+  const float *ref_rel_rot;        /* (4,26,3,3) */
+  const float *world_loc;
+  const float *world_rot;
+  const float *initial_rel_rot;
+  float *bones;
+  float *root;
+  float *final_rel_rot;
+  float *out_relative_pose_rot;
+} p2c_lift_desc;
+P2C_API int p2c_lift_supported(const p2c_lift_desc *desc);   /* 1 = the model geometry, kind and precision the kernel covers */
+P2C_API int p2c_lift_fwd(const p2c_lift_desc *desc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

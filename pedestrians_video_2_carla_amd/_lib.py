@@ -58,6 +58,14 @@ class TrainStepDesc(ctypes.Structure):
     _fields_ = [('head', PoseHeadDesc), ('mlp', MlpDesc), ('pair_counts', _f32p)]
 
 
+class LiftDesc(ctypes.Structure):
+    """Mirror of ``p2c_lift_desc`` (include/p2c.h)."""
+    _fields_ = [('mlp', MlpDesc), ('B', _i32), ('T', _i32), ('kind', _i32), ('max_blocks', _i32), ('skel_type', _f32p),
+                ('ref_rel_loc', _f32p), ('ref_rel_rot', _f32p), ('world_loc', _f32p), ('world_rot', _f32p),
+                ('initial_rel_rot', _f32p), ('bones', _f32p), ('root', _f32p), ('final_rel_rot', _f32p),
+                ('out_relative_pose_rot', _f32p)]
+
+
 # every symbol include/p2c.h declares: (restype, argtypes)
 _vp, _i64, _ip = ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32)
 class AdamWDesc(ctypes.Structure):
@@ -320,6 +328,8 @@ SYMBOLS = {
     'p2c_heatmap_keypoints_fwd': (ctypes.c_int, [ctypes.POINTER(HeatmapKeypointsDesc), _vp]),
     'p2c_carla_pose_fwd': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     'p2c_carla_pose_inv': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
+    'p2c_lift_supported': (ctypes.c_int, [ctypes.POINTER(LiftDesc)]),
+    'p2c_lift_fwd': (ctypes.c_int, [ctypes.POINTER(LiftDesc), _vp]),
 }
 
 _lib = None

@@ -28,11 +28,12 @@
 
 #include "../../include/p2c.h"
 
+#include "p2c_carla_dev.h"   // kDeg, kRad, clamp_unit, carla_row: shared with K32 (p2c_lift.hip)
+
 namespace p2c_carla {
 
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;   // 8 workgroups per CU on 256 CUs
-constexpr float kDeg = 57.29577951308232f, kRad = 0.017453292519943295f;
 
 struct FwdArgs {
   const float *rel_loc, *rel_rot, *world_loc, *world_rot;
@@ -46,10 +47,6 @@ struct InvArgs {
   int64_t n_bones;
 };
 
-__device__ __forceinline__ float clamp_unit(float v) {            // comparisons, not fminf / fmaxf: a NaN stays a NaN
-  return v > 1.0f ? 1.0f : (v < -1.0f ? -1.0f : v);
-}
-
 __global__ __launch_bounds__(kThreads) void carla_pose_fwd_kernel(FwdArgs a) {
   const int64_t step = (int64_t)gridDim.x * kThreads;
   for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < a.n_total; e += step) {
@@ -59,12 +56,7 @@ __global__ __launch_bounds__(kThreads) void carla_pose_fwd_kernel(FwdArgs a) {
     const float *r = (is_root ? a.world_rot : a.rel_rot) + row * 9;
     const float x = p[0], y = p[1], z = p[2];
     const float r00 = r[0], r01 = r[1], r02 = r[2], r12 = r[5], r22 = r[8];
-    const float e1 = asinf(clamp_unit(r02));
-    const float e0 = atan2f(-r12, r22);
-    const float e2 = atan2f(-r01, r00);
-    float *o = (is_root ? a.root : a.bones) + row * 6;
-    o[0] = x, o[1] = y, o[2] = -z;
-    o[3] = -(e1 * kDeg), o[4] = -(e2 * kDeg), o[5] = -(e0 * kDeg);
+    carla_row(x, y, z, r00, r01, r02, r12, r22, (is_root ? a.root : a.bones) + row * 6);
   }
 }
 

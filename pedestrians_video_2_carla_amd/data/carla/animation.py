@@ -17,11 +17,34 @@ def save_carla_animation(path: str, outputs, fps: float = 30.0) -> str:
     outputs = list(outputs)
     if not outputs:
         raise ValueError('no predictions to save')
-    bones, roots, ages, genders = [], [], [], []
+    rows = []
     for sliced, meta in outputs:
         b, r = export_clips(sliced)
         if r is None:
             raise KeyError('world_loc / world_rot are missing from the predictions: no root transform to store')
+        rows.append((b, r, meta))
+    return _write(path, rows, fps)
+
+
+def lift_carla_animation(path: str, flow, batches, fps: float = 30.0) -> str:
+    """The file ``save_carla_animation(path, trainer.predict(flow, batches), fps)`` writes, from ``Trainer.predict_carla``:
+    a LinearAE flow takes one launch per batch (K32) and no pose tensor is materialised; bones and root travel to the host
+    together, one copy per batch. ``batches``: ``(frames, targets, meta)`` as for ``predict``."""
+    import torch
+    from pedestrians_video_2_carla_amd.trainer import Trainer
+    rows = []
+    for bones, root, meta in Trainer().predict_carla(flow, batches):
+        both = torch.cat((bones, root.unsqueeze(-2)), -2).cpu().numpy()
+        rows.append((both[..., :-1, :], both[..., -1, :], meta))
+    if not rows:
+        raise ValueError('no predictions to save')
+    return _write(path, rows, fps)
+
+
+def _write(path: str, rows, fps: float) -> str:
+    """``rows``: per batch (bones (n,T,J,6), root (n,T,6), meta) on the host."""
+    bones, roots, ages, genders = [], [], [], []
+    for b, r, meta in rows:
         n = len(b)
         bones.append(b)
         roots.append(r)

@@ -3348,3 +3348,189 @@ def carla_pose_import(bones: Tensor, max_blocks: int = 0) -> Tuple[Tensor, Tenso
         _lib.check(lib.p2c_carla_pose_inv(rows.data_ptr(), loc.data_ptr(), rot.data_ptr(), n, n_joints, int(max_blocks),
                                           _stream()), 'p2c_carla_pose_inv')
     return loc, rot
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# keypoint clips -> CARLA bone transforms in one launch (K32, csrc/p2c_lift.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+LIFT_KINDS = ('pose_changes_6d', 'relative_rot_6d')
+
+
+def lift_framework() -> bool:
+    """P2C_LIFT_FRAMEWORK=1: ``lift_to_carla`` runs the three separate calls (``fused_mlp`` -> ``pose_head`` ->
+    ``carla_pose_export``) on the device: the comparison arm of tools/bench_lift.py."""
+    return os.environ.get('P2C_LIFT_FRAMEWORK', '0') == '1'
+
+
+def lift_supported(dims: Sequence[int]) -> bool:
+    """The model geometry K32 is compiled for: the LinearAE 52-26-13-6-39-78-156 (fp32, the two 6-D kinds)."""
+    dims = [int(v) for v in dims]
+    if not 2 <= len(dims) <= _lib.P2C_MLP_MAX_LAYERS + 1:
+        return False
+    d = _lib.LiftDesc()
+    d.mlp.n_layers = len(dims) - 1
+    for i, v in enumerate(dims):
+        d.mlp.dims[i] = v
+    d.kind = KIND['pose_changes_6d']
+    return bool(_lib.lib().p2c_lift_supported(ctypes.byref(d)))
+
+
+def _fma32(a: Tensor, b: Tensor, c: Tensor) -> Tensor:
+    """fmaf(a, b, c) on fp32 tensors, bit for bit, from fp64 tensor ops: the product of two fp32 values is exact in fp64; the
+    sum is rounded to odd (TwoSum gives the rounding error of the nearest-even sum; where it is non-zero and the sum's last
+    bit is even, the neighbour on the error's side is the odd one), and a value rounded to odd with 29 spare bits rounds to
+    fp32 as the exact sum does."""
+    p, c = a.double() * b.double(), c.double()
+    s = p + c
+    t = s - p
+    err = (p - (s - t)) + (c - t)
+    even = (s.view(torch.int64) & 1) == 0
+    side = torch.where(err > 0, torch.full_like(s, float('inf')), torch.full_like(s, float('-inf')))
+    return torch.where((err != 0) & even & torch.isfinite(s), torch.nextafter(s, side), s).float()
+
+
+def _mul3_fma(a: Tensor, b: Tensor) -> Tensor:
+    """a @ b for (...,3,3) fp32 in the order of the kernels' ``mul``: fmaf(a_i0, b_0k, fmaf(a_i1, b_1k, a_i2 * b_2k))."""
+    a0, a1, a2 = (a[..., :, k, None] for k in range(3))          # (...,3,1) columns of a
+    b0, b1, b2 = (b[..., None, k, :] for k in range(3))          # (...,1,3) rows of b
+    return _fma32(a0, b0, _fma32(a1, b1, a2 * b2))
+
+
+def _lift_chain(changes: Tensor, start: Tensor, exact_fma: bool) -> Tensor:
+    """R_t = c_t @ R_{t-1} over the frames (reference projection.py:190-193), R_{-1} = ``start`` (B,J,3,3)."""
+    prev, rel = start, []
+    for t in range(changes.shape[1]):
+        prev = _mul3_fma(changes[:, t], prev) if exact_fma else changes[:, t] @ prev
+        rel.append(prev)
+    return torch.stack(rel, 1)
+
+
+def _lift_world(B, T, world_loc, world_rot, like: Tensor):
+    if world_loc is not None:
+        return world_loc, world_rot
+    return (torch.zeros(B, T, 3, dtype=like.dtype, device=like.device),
+            torch.eye(3, dtype=like.dtype, device=like.device).expand(B, T, 3, 3).contiguous())
+
+
+@torch.no_grad()
+def pose_to_carla_rows(y: Tensor, skel_type: Tensor, kind: str, world_loc: Optional[Tensor] = None,
+                       world_rot: Optional[Tensor] = None, initial_rel_rot: Optional[Tensor] = None, want_rot: bool = False,
+                       max_blocks: int = 0, tensor_ops: bool = False):
+    """A movements model's rotation output -> ``(bones, root, final_rel_rot, relative_pose_rot | None)`` as ``lift_to_carla``
+    returns them: the two calls behind the model in the composed path. ``kind``: 'pose_changes_6d' / 'relative_rot_6d' with
+    ``y`` (B,T,26,6), 'pose_changes' / 'relative_rot' with (B,T,26,3,3). fp32 device tensors take the materialising pose head and
+    K30; the pose head starts every clip from the reference pose, so with ``initial_rel_rot`` its pose changes are multiplied up
+    again from there in the order of its own 3x3 product (``_mul3_fma``). Host tensors, other dtypes and ``tensor_ops`` take the
+    definition on tensor ops (reference projection.py:144-195 and ``carla_pose_export``'s)."""
+    B, T = y.shape[:2]
+    scan = kind.startswith('pose_changes')
+    wl, wr = _lift_world(B, T, world_loc, world_rot, y)
+    if not tensor_ops and y.is_cuda and y.dtype == torch.float32 and not torch.is_autocast_enabled():
+        carry = scan and initial_rel_rot is not None
+        want = ('relative_pose_loc', 'relative_pose_rot') + (('pose_changes',) if carry else ())
+        _, outs = pose_head(y, PoseHeadSpec(kind=kind, transform='none'), skel_type, want=want)
+        rot = _lift_chain(outs['pose_changes'], initial_rel_rot, exact_fma=True) if carry else outs['relative_pose_rot']
+        bones, root = carla_pose_export(outs['relative_pose_loc'], rot, wl, wr, max_blocks=max_blocks)
+    else:
+        from pedestrians_video_2_carla_amd.transforms.rotation_conversions import rotation_6d_to_matrix
+        m = rotation_6d_to_matrix(y) if kind.endswith('6d') else y
+        ref_loc, ref_rot = ref.get_relative_tensors(y.device, dtype=y.dtype)
+        st = skel_type.long()
+        rot = _lift_chain(m, initial_rel_rot if initial_rel_rot is not None else ref_rot[st], exact_fma=False) if scan else m
+        bones, root = _carla_row(ref_loc[st][:, None].expand(B, T, J, 3), rot), _carla_row(wl, wr)
+    return bones, root, (rot[:, -1].clone() if scan else None), (rot.contiguous() if want_rot else None)
+
+
+def _linear_stack(x2d: Tensor, weights, biases) -> Tensor:
+    h = x2d
+    for l, (w, b) in enumerate(zip(weights, biases)):
+        h = torch.nn.functional.linear(h, w, b)
+        if l < len(weights) - 1:
+            h = torch.relu(h)
+    return h
+
+
+@torch.no_grad()
+def lift_to_carla(frames: Tensor, weights: Sequence[Tensor], biases: Sequence[Tensor], skel_type: Tensor,
+                  kind: str = 'pose_changes_6d', image: Optional[Tensor] = None, image_is_current: bool = False,
+                  world_loc: Optional[Tensor] = None, world_rot: Optional[Tensor] = None,
+                  initial_rel_rot: Optional[Tensor] = None, want_rot: bool = False,
+                  max_blocks: int = 0) -> Tuple[Tensor, Tensor, Optional[Tensor], Optional[Tensor]]:
+    """2-D keypoint clips -> the rows a CARLA walker consumes. ``frames`` (B,T,26,2) or (B,T,52), the LinearAE's ``weights`` /
+    ``biases`` (as ``fused_mlp`` takes them), ``skel_type`` (B) -> ``bones`` (B,T,26,6), ``root`` (B,T,6) (the identity world's
+    row without ``world_loc`` (B,T,3) / ``world_rot`` (B,T,3,3), which come together), ``final_rel_rot`` (B,26,3,3) (the last
+    relative rotation, pose_changes kind; None otherwise) and, with ``want_rot``, ``relative_pose_rot`` (B,T,26,3,3).
+    ``initial_rel_rot`` (B,26,3,3): where the running rotation of the pose_changes kind starts instead of the reference pose --
+    hand a clip the previous clip's ``final_rel_rot`` and a cut video yields the rows of the uncut one.
+    fp32 device tensors of the 52-26-13-6-39-78-156 model take K32: one launch (two when ``image`` -- ``mlp_image_layout``
+    floats -- is not given or not ``image_is_current``: the weights are packed first), with the bits of the three separate calls.
+    ``P2C_LIFT_FRAMEWORK=1`` runs those calls; host tensors, fp64 and other geometries the same composition on tensor ops.
+    A predict-time operation: nothing is recorded for autograd. ``max_blocks`` lowers the grid cap (tests)."""
+    if kind not in LIFT_KINDS:
+        raise RuntimeError(f'lift_to_carla: kind {kind!r}; one of {LIFT_KINDS} expected')
+    if frames.ndim not in (3, 4) or len(weights) != len(biases) or not weights:
+        raise RuntimeError(f'lift_to_carla: frames (B,T,26,2) or (B,T,52) expected, got {tuple(frames.shape)}')
+    B, T = frames.shape[:2]
+    x = frames.reshape(B, T, -1)
+    dims = [weights[0].shape[1]] + [w.shape[0] for w in weights]
+    if x.shape[-1] != dims[0] or dims[-1] != J * 6:
+        raise RuntimeError(f'lift_to_carla: frames of {x.shape[-1]} values for a model {dims[0]} -> {dims[-1]}; '
+                           f'{dims[0]} -> {J * 6} expected')
+    if tuple(skel_type.shape) != (B,):
+        raise RuntimeError(f'skel_type should have shape ({B},), got {tuple(skel_type.shape)}')
+    if (world_loc is None) != (world_rot is None):
+        raise RuntimeError('lift_to_carla: world_loc and world_rot come together or not at all')
+    if world_loc is not None and (tuple(world_loc.shape) != (B, T, 3) or tuple(world_rot.shape) != (B, T, 3, 3)):
+        raise RuntimeError(f'lift_to_carla: world tensors {tuple(world_loc.shape)}, {tuple(world_rot.shape)}; '
+                           f'{(B, T, 3)} and {(B, T, 3, 3)} expected')
+    if initial_rel_rot is not None and tuple(initial_rel_rot.shape) != (B, J, 3, 3):
+        raise RuntimeError(f'initial_rel_rot should have shape {(B, J, 3, 3)}, got {tuple(initial_rel_rot.shape)}')
+    floats = [x, *weights, *biases] + [t for t in (world_loc, world_rot, initial_rel_rot) if t is not None]
+    if B == 0 or T == 0:
+        e = dict(dtype=x.dtype, device=x.device)
+        return (torch.empty(B, T, J, 6, **e), torch.empty(B, T, 6, **e),
+                torch.empty(B, J, 3, 3, **e) if kind == 'pose_changes_6d' else None,
+                torch.empty(B, T, J, 3, 3, **e) if want_rot else None)
+    on_device = (all(t.is_cuda and t.dtype == torch.float32 and t.device == x.device for t in floats)
+                 and skel_type.device == x.device and not torch.is_autocast_enabled())
+    if not (on_device and lift_supported(dims)):
+        y = _linear_stack(x.reshape(B * T, -1), weights, biases).view(B, T, J, 6)
+        return pose_to_carla_rows(y, skel_type, kind, world_loc, world_rot, initial_rel_rot, want_rot, tensor_ops=True)
+    x = x.detach().contiguous()
+    weights, biases = [w.detach().contiguous() for w in weights], [b.detach().contiguous() for b in biases]
+    skel_type = _require_device(skel_type, 'skel_type', torch.int32)
+    wl = world_loc.detach().contiguous() if world_loc is not None else None
+    wr = world_rot.detach().contiguous() if world_rot is not None else None
+    init = initial_rel_rot.detach().contiguous() if initial_rel_rot is not None else None
+    if lift_framework():
+        y = fused_mlp(x.view(B * T, -1), weights, biases, image=image, image_is_current=image_is_current).view(B, T, J, 6)
+        return pose_to_carla_rows(y, skel_type, kind, wl, wr, init, want_rot, max_blocks)
+    lib = _lib.lib()
+    n_image = lib.p2c_mlp_image_floats(ctypes.byref(_mlp_desc(x.view(B * T, -1), weights, biases)))
+    if image is None:
+        image, image_is_current = torch.empty(n_image, dtype=torch.float32, device=x.device), False
+    elif image.numel() != n_image or image.device != x.device or image.dtype != torch.float32:
+        raise RuntimeError('packed weight image of the wrong size / device')
+    f32 = dict(dtype=torch.float32, device=x.device)
+    bones, root = torch.empty(B, T, J, 6, **f32), torch.empty(B, T, 6, **f32)
+    final = torch.empty(B, J, 3, 3, **f32) if kind == 'pose_changes_6d' else None
+    rot = torch.empty(B, T, J, 3, 3, **f32) if want_rot else None
+    d = _lift_desc(x, weights, biases, skel_type, kind, image, image_is_current, wl, wr, init, bones, root, final, rot, max_blocks)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.p2c_lift_fwd(ctypes.byref(d), _stream()), 'p2c_lift_fwd')
+    return bones, root, final, rot
+
+
+def _lift_desc(x, weights, biases, skel_type, kind, image, image_is_current, world_loc, world_rot, initial_rel_rot, bones, root,
+               final_rel_rot, rot, max_blocks=0):
+    """``p2c_lift_desc`` over contiguous fp32 device tensors (x (B,T,52), skel_type int32)."""
+    B, T = x.shape[:2]
+    d = _lib.LiftDesc()
+    d.mlp = _mlp_desc(x.view(B * T, -1), weights, biases)
+    d.mlp.w_image, d.mlp.skip_pack = image.data_ptr(), int(bool(image_is_current))
+    d.B, d.T, d.kind, d.max_blocks = B, T, KIND[kind], int(max_blocks)
+    ref_loc, ref_rot = ref.get_relative_tensors(x.device)
+    d.skel_type, d.ref_rel_loc, d.ref_rel_rot = skel_type.data_ptr(), ref_loc.data_ptr(), ref_rot.data_ptr()
+    d.world_loc, d.world_rot, d.initial_rel_rot = _ptr(world_loc), _ptr(world_rot), _ptr(initial_rel_rot)
+    d.bones, d.root, d.final_rel_rot, d.out_relative_pose_rot = bones.data_ptr(), _ptr(root), _ptr(final_rel_rot), _ptr(rot)
+    return d

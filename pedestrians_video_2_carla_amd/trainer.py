@@ -695,6 +695,22 @@ class Trainer:
         finally:
             flow.train(was_training)
 
+    def predict_carla(self, flow, batches: Iterable) -> List:
+        """The predict loop for a CARLA player: per batch ``(bones (B,T,26,6), root (B,T,6), meta)``, the rows
+        ``export_clips(flow.predict_step(batch))`` would give, left on the batch's device. A LinearAE flow takes one launch per
+        batch (K32, ``walker_control.carla_lifter.CarlaLifter``); other movements models the composed path. Eval mode, no
+        gradients, the flow's train / eval mode is put back afterwards."""
+        from pedestrians_video_2_carla_amd.walker_control.carla_lifter import CarlaLifter
+        lifter = CarlaLifter(flow)
+        was_training = flow.training
+        flow.eval()
+        try:
+            with torch.no_grad():
+                return [(*lifter.lift(batch[0], batch[2]), batch[2]) for batch in batches]
+        finally:
+            flow.train(was_training)
+            lifter.close()
+
     def fit(self, flow, datamodule, batches: Optional[Iterable] = None):
         self.setup(flow, datamodule)
         device = self.device or flow.device
