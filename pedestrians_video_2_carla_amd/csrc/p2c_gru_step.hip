@@ -1,5 +1,6 @@
 // p2c_gru_step.hip -- K23: the recurrent half of a GRU layer for any hidden size (1 <= H <= 1024), one launch per time step
-// (gfx950, fp32 MFMA). The tiling, the staging and the launch-per-step seam are K18's (p2c_lstm_step.hip).
+// (gfx950, fp32 MFMA). The launch-per-step seam is K18's (p2c_lstm_step.hip); the tile (its constants, the staging and both MFMA
+// loops) is p2c_rec_step_dev.h's, shared with K18.
 //
 // torch.nn.GRU, gate order r, z, n, with gx[t] = x[t] W_ih^T + b_ih from the caller (one dense GEMM for all t):
 //   r = sigmoid(gx_r + W_hr h + b_hr)     z = sigmoid(gx_z + W_hz h + b_hz)     n = tanh(gx_n + r (W_hn h + b_hn))
@@ -16,24 +17,16 @@
 // Backward, step t (descending): dh = g_out[t] (+ g_hT at T - 1) + z[t+1] dh[t+1] (carried through a (B, H) workspace that only
 // the owning lane touches) + g_gh[t+1] W_hh[:, units] (K = 3H, staged the same way); it writes g_gx[t], g_gh[t] and the carry.
 // One more launch forms g_h0 = carry + g_gh[0] W_hh. The weight gradients are the caller's (K12 over all (t, b)).
-// Addresses are 64-bit; rows past B / H are range-checked (loads are clamped, stores are skipped). The staging loads of a chunk
-// are all issued first, unconditionally, from clamped (always valid) addresses; the zero padding is a select on the LDS write.
+// Addresses are 64-bit; rows past B / H are range-checked (loads are clamped, stores are skipped).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/p2c.h"
-#include "p2c_rec_dev.h"
+#include "p2c_rec_step_dev.h"
 
 namespace p2c_gru_step {
 
-using namespace p2c_rec;
-constexpr int BM = 32;            // sequences per workgroup (16 per wave)
-constexpr int NT = 64 * BM / 16;  // threads per workgroup
-constexpr int KC = 64;            // K chunk staged in LDS
-constexpr int KP = KC + 4;        // LDS pitch: the 16 rows x 4 k of a fragment read fall in distinct banks (two passes)
-
-// a value loaded from global memory made resident here: the load cannot be sunk under the select that follows
-__device__ __forceinline__ void pin1(float &v) { asm volatile("" : "+v"(v)); }
+using namespace p2c_rec_step;
 
 struct Args {
   const float *gx, *h0, *w_hh, *bias_hh;
@@ -45,18 +38,15 @@ struct Args {
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NT) void gru_step_fwd_kernel(const Args a, const int t) {
-  __shared__ float wl[48 * KP];   // rows q * 16 + i: W_hh row q H + ub + i, columns k0 .. k0 + KC
-  __shared__ float hl[BM * KP];   // rows s: h[t-1] of sequence b0 + s
+  __shared__ float wl[3 * 16 * KP], hl[BM * KP];             // gates_product's
   const int H = a.H, B = a.B, T = a.T;
   const int64_t G = 3 * (int64_t)H;
-  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4, w = threadIdx.x >> 6;
-  const int b0 = blockIdx.x * BM, ub = blockIdx.y * 16;
-  const int b = b0 + w * 16 + c, u0 = ub + 4 * g;         // this lane: sequence b, units u0 .. u0 + 3
-  const bool bok = b < B;
+  const Lane l(B);
+  const int b = l.b, u0 = l.u0, bc = l.bc;                    // this lane: sequence b, units u0 .. u0 + 3
+  const bool bok = l.bok;
 
   const float *hp = t > 0 ? a.out + ((int64_t)(t - 1) * B) * H : a.h0;   // NULL at t = 0 with the zero state: no product
   // per-lane rows: unconditional loads from clamped addresses (one round trip for all of them)
-  const int bc = min(b, B - 1);
   f32x4 acc[3], xn, hprev;        // acc[0], acc[1]: the r and z pre-activations; acc[2]: hn = W_hn h + b_hn; xn: gx_n
   {
     const float *gxr = a.gx + ((int64_t)t * B + bc) * G;
@@ -77,43 +67,7 @@ __global__ __launch_bounds__(NT) void gru_step_fwd_kernel(const Args a, const in
     }
   }
 
-  if (hp) {
-    for (int k0 = 0; k0 < H; k0 += KC) {
-      constexpr int NW_ = 48 * KC / NT, NH_ = BM * KC / NT;
-      float vw[NW_], vh[NH_];
-#pragma unroll
-      for (int j = 0; j < NW_; ++j) {
-        const int e = threadIdx.x + j * NT, row = e / KC, k = e % KC, u = ub + (row & 15), kk = k0 + k;
-        vw[j] = a.w_hh[((int64_t)(row >> 4) * H + min(u, H - 1)) * H + min(kk, H - 1)];
-      }
-#pragma unroll
-      for (int j = 0; j < NH_; ++j) {
-        const int e = threadIdx.x + j * NT, s = e / KC, k = e % KC, kk = k0 + k;
-        vh[j] = hp[(int64_t)min(b0 + s, B - 1) * H + min(kk, H - 1)];
-      }
-#pragma unroll
-      for (int j = 0; j < NW_; ++j) {
-        pin1(vw[j]);
-        const int e = threadIdx.x + j * NT, row = e / KC, k = e % KC, u = ub + (row & 15), kk = k0 + k;
-        wl[row * KP + k] = (u < H && kk < H) ? vw[j] : 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < NH_; ++j) {
-        pin1(vh[j]);
-        const int e = threadIdx.x + j * NT, s = e / KC, k = e % KC, kk = k0 + k;
-        hl[s * KP + k] = (b0 + s < B && kk < H) ? vh[j] : 0.f;
-      }
-      __syncthreads();
-      const int nks = (min(KC, H - k0) + 3) / 4;            // k-steps that touch a real column (the rest of the chunk is 0)
-      const float *wa = wl + c * KP + g, *hb = hl + (w * 16 + c) * KP + g;
-      for (int ks = 0; ks < nks; ++ks) {
-        const float bv = hb[4 * ks];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[q * 16 * KP + 4 * ks], bv, acc[q], 0, 0, 0);
-      }
-      __syncthreads();                                      // the chunk has been read before the next one is staged
-    }
-  }
+  if (hp) gates_product<3>(acc, wl, hl, a.w_hh, hp, H, B, l);
 
   if (!bok) return;
   const int64_t row1 = ((int64_t)t * B + b) * H, row4 = ((int64_t)t * B + b) * 4 * (int64_t)H;
@@ -133,15 +87,12 @@ __global__ __launch_bounds__(NT) void gru_step_fwd_kernel(const Args a, const in
 // ---- backward ---------------------------------------------------------------------------------------------------------------
 // t >= 0: step t of the backward; t = -1: g_h0 = carry + g_gh[0] W_hh only.
 __global__ __launch_bounds__(NT) void gru_step_bwd_kernel(const Args a, const int t) {
-  __shared__ float wl[16 * KP];   // rows i: W_hh[k0 + k][ub + i] (the transposed column block of the tile's units)
-  __shared__ float gl[BM * KP];   // rows s: g_gh[t+1] of sequence b0 + s
+  __shared__ float wl[16 * KP], gl[BM * KP];                  // state_grad_product's
   const int H = a.H, B = a.B, T = a.T;
   const int64_t G = 3 * (int64_t)H;
-  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4, w = threadIdx.x >> 6;
-  const int b0 = blockIdx.x * BM, ub = blockIdx.y * 16;
-  const int b = b0 + w * 16 + c, u0 = ub + 4 * g;
-  const bool bok = b < B;
-  const int bc = min(b, B - 1);
+  const Lane l(B);
+  const int b = l.b, u0 = l.u0, bc = l.bc;
+  const bool bok = l.bok;
 
   // the saved rows of the step: requested before the product, used after it (lanes past B / H compute values that are never stored)
   f32x4 ar, az, an, hn, hprev, go;
@@ -165,48 +116,8 @@ __global__ __launch_bounds__(NT) void gru_step_bwd_kernel(const Args a, const in
     }
   }
 
-  // g_gh[t+1] W_hh[:, units]: four accumulators over the k-steps break the dependent MFMA chain
-  f32x4 e[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) e[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  if (t + 1 < T) {
-    const float *gn = a.g_gh + ((int64_t)(t + 1) * B) * G;
-    for (int64_t k0 = 0; k0 < G; k0 += KC) {
-      constexpr int NW_ = 16 * KC / NT, NG_ = BM * KC / NT;
-      float vw[NW_], vg[NG_];
-#pragma unroll
-      for (int j = 0; j < NW_; ++j) {
-        const int x = threadIdx.x + j * NT, k = x / 16, i = x % 16;
-        vw[j] = a.w_hh[min(k0 + k, G - 1) * H + min(ub + i, H - 1)];
-      }
-#pragma unroll
-      for (int j = 0; j < NG_; ++j) {
-        const int x = threadIdx.x + j * NT, s = x / KC, k = x % KC;
-        vg[j] = gn[(int64_t)min(b0 + s, B - 1) * G + min(k0 + k, G - 1)];
-      }
-#pragma unroll
-      for (int j = 0; j < NW_; ++j) {
-        pin1(vw[j]);
-        const int x = threadIdx.x + j * NT, k = x / 16, i = x % 16;
-        wl[i * KP + k] = (ub + i < H && k0 + k < G) ? vw[j] : 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < NG_; ++j) {
-        pin1(vg[j]);
-        const int x = threadIdx.x + j * NT, s = x / KC, k = x % KC;
-        gl[s * KP + k] = (b0 + s < B && k0 + k < G) ? vg[j] : 0.f;
-      }
-      __syncthreads();
-      const int n16 = (int)((min((int64_t)KC, G - k0) + 15) / 16);   // groups of four k-steps that touch a real row of W_hh
-      const float *wa = wl + c * KP + g, *gb = gl + (w * 16 + c) * KP + g;
-      for (int j = 0; j < n16; ++j) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) e[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[16 * j + 4 * q], gb[16 * j + 4 * q], e[q], 0, 0, 0);
-      }
-      __syncthreads();
-    }
-  }
-  const f32x4 dhr = (e[0] + e[1]) + (e[2] + e[3]);
+  // g_gh[t+1] W_hh[:, units]
+  const f32x4 dhr = state_grad_product(wl, gl, a.w_hh, t + 1 < T ? a.g_gh + ((int64_t)(t + 1) * B) * G : nullptr, G, H, B, l);
   if (!bok) return;
 
   if (t < 0) {
@@ -236,7 +147,7 @@ using namespace p2c_gru_step;
 
 static int check_steps(const p2c_gru_desc *d, Args &a) {
   if (!d || !d->w_hh) return P2C_E_NULL;
-  if (d->T < 0 || d->B < 0 || d->B > (1 << 20) || d->H < 1 || d->H > 1024) return P2C_E_SHAPE;
+  if (int rc = check_tbh(d->T, d->B, d->H)) return rc;
   // fields this form does not implement are refused, not ignored
   if (d->gx_bt || d->out_drop || d->drop_state) return P2C_E_SHAPE;
   a = Args{};
@@ -247,11 +158,7 @@ static int check_steps(const p2c_gru_desc *d, Args &a) {
   return 0;
 }
 
-static dim3 steps_grid(const Args &a) { return dim3((unsigned)((a.B + BM - 1) / BM), (unsigned)((a.H + 15) / 16)); }
-
-extern "C" int64_t p2c_gru_steps_workspace_floats(int32_t B, int32_t H) {
-  return (B < 0 || H < 0) ? 0 : (int64_t)B * H;
-}
+extern "C" int64_t p2c_gru_steps_workspace_floats(int32_t B, int32_t H) { return workspace_floats(B, H); }
 
 extern "C" int p2c_gru_steps_fwd(const p2c_gru_desc *d, void *stream) {
   Args a;
@@ -259,7 +166,7 @@ extern "C" int p2c_gru_steps_fwd(const p2c_gru_desc *d, void *stream) {
   if (rc) return rc;
   if (!a.gx || !a.out) return P2C_E_NULL;                        // out carries the state from one launch to the next
   if (a.B == 0) return 0;
-  for (int t = 0; t < a.T; ++t) hipLaunchKernelGGL(gru_step_fwd_kernel, steps_grid(a), dim3(NT), 0, (hipStream_t)stream, a, t);
+  for (int t = 0; t < a.T; ++t) hipLaunchKernelGGL(gru_step_fwd_kernel, steps_grid(a.B, a.H), dim3(NT), 0, (hipStream_t)stream, a, t);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
@@ -273,8 +180,8 @@ extern "C" int p2c_gru_steps_bwd(const p2c_gru_desc *d, float *workspace, void *
   if ((a.T > 1 || a.g_h0) && !workspace) return P2C_E_NULL;
   a.dh = workspace;
   if (a.B == 0 || a.T == 0) return 0;
-  for (int t = a.T - 1; t >= 0; --t) hipLaunchKernelGGL(gru_step_bwd_kernel, steps_grid(a), dim3(NT), 0, (hipStream_t)stream, a, t);
-  if (a.g_h0) hipLaunchKernelGGL(gru_step_bwd_kernel, steps_grid(a), dim3(NT), 0, (hipStream_t)stream, a, -1);
+  for (int t = a.T - 1; t >= 0; --t) hipLaunchKernelGGL(gru_step_bwd_kernel, steps_grid(a.B, a.H), dim3(NT), 0, (hipStream_t)stream, a, t);
+  if (a.g_h0) hipLaunchKernelGGL(gru_step_bwd_kernel, steps_grid(a.B, a.H), dim3(NT), 0, (hipStream_t)stream, a, -1);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }

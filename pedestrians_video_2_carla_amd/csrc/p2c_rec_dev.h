@@ -1,4 +1,5 @@
-// p2c_rec_dev.h -- device helpers shared by the time-loop kernels (K7b p2c_lstm.hip, K7c p2c_s2s.hip).
+// p2c_rec_dev.h -- device helpers shared by the time-loop kernels (K7b p2c_lstm.hip, K7c p2c_s2s.hip) and, through
+// p2c_rec_step_dev.h, by the one-launch-per-step recurrences (K18 p2c_lstm_step.hip, K23 p2c_gru_step.hip).
 //
 // A recurrence step is ~1.3 us of MFMA + transcendental work; one exposed memory round trip per step doubles it. Two rules
 // keep the loop body free of them:

@@ -1149,10 +1149,32 @@ def lstm_supported(hidden_size: int) -> bool:
     return hidden_size in (16, 32, 48, 64, 96, 128)
 
 
+REC_STEPS_MAX_HIDDEN = 1024      # the widest layer of the one-launch-per-step recurrences (K18, K23: csrc/p2c_rec_step_dev.h)
+
+
 def lstm_steps_supported(hidden_size: int) -> bool:
-    """The widths of the one-launch-per-step recurrence (K18, p2c_lstm_steps_*): any 1 <= H <= 1024. ``lstm_layer`` takes it
-    for every width outside ``lstm_supported``."""
-    return 1 <= hidden_size <= 1024
+    """The widths of the one-launch-per-step recurrence (K18, p2c_lstm_steps_*): any 1 <= H <= REC_STEPS_MAX_HIDDEN.
+    ``lstm_layer`` takes it for every width outside ``lstm_supported``."""
+    return 1 <= hidden_size <= REC_STEPS_MAX_HIDDEN
+
+
+def _dense_grad(g: Optional[Tensor], name: str) -> Optional[Tensor]:
+    """An optional incoming gradient, dense on the device. Keep it in a local: a strided one is a copy the launch has to outlive."""
+    return None if g is None else _require_device(g, name)
+
+
+def _recurrent_weight_grad(g: Tensor, out: Tensor, h0: Tensor, w_hh: Tensor, zero_state: bool) -> Optional[Tensor]:
+    """dW_hh = sum_t g[t]^T h[t-1] over all (t, b) (K12), g (T,B,G) the gradient of the recurrent pre-activations. None: it was
+    added into w_hh.grad (the gradient sink)."""
+    sink = _sink(w_hh)
+    g_w, acc = sink, sink is not None
+    if out.shape[0] > 1:
+        g_w, acc = atb(g[1:].reshape(-1, g.shape[2]), out[:-1].reshape(-1, out.shape[2]), out=g_w, accumulate=acc)[0], True
+    if not zero_state:                # the t = 0 term meets the initial state (zero state: no contribution)
+        g_w = atb(g[0], h0, out=g_w, accumulate=acc)[0]
+    if sink is not None:
+        return None
+    return torch.zeros_like(w_hh) if g_w is None else g_w
 
 
 class LSTMRecurrenceFunction(torch.autograd.Function):
@@ -1175,7 +1197,7 @@ class LSTMRecurrenceFunction(torch.autograd.Function):
         ctx.steps = not lstm_supported(H)                     # K18 for the widths K7b does not cover
         if ctx.steps and not lstm_steps_supported(H):
             raise RuntimeError(f'hidden size {H} is not supported by the HIP recurrence (16, 32, 48, 64, 96, 128 in one launch, '
-                               f'any other 1 ... 1024 one launch per step)')
+                               f'any other 1 ... {REC_STEPS_MAX_HIDDEN} one launch per step)')
         f32 = dict(dtype=torch.float32, device=gx.device)
         out, hT, cT = torch.empty(T, B, H, **f32), torch.empty(B, H, **f32), torch.empty(B, H, **f32)
         acts, cs = torch.empty(T, B, 4 * H, **f32), torch.empty(T, B, H, **f32)
@@ -1208,10 +1230,7 @@ class LSTMRecurrenceFunction(torch.autograd.Function):
         if not zero:
             g_h0, g_c0 = torch.empty(B, H, **f32), torch.empty(B, H, **f32)
             d.c0, d.g_h0, d.g_c0 = c0.data_ptr(), g_h0.data_ptr(), g_c0.data_ptr()
-        # (locals: a strided gradient is copied, and the copy has to outlive the launch that reads it)
-        g_out = None if g_out is None else _require_device(g_out, 'grad out')
-        g_hT = None if g_hT is None else _require_device(g_hT, 'grad hT')
-        g_cT = None if g_cT is None else _require_device(g_cT, 'grad cT')
+        g_out, g_hT, g_cT = _dense_grad(g_out, 'grad out'), _dense_grad(g_hT, 'grad hT'), _dense_grad(g_cT, 'grad cT')
         d.g_out, d.g_hT, d.g_cT = _ptr(g_out), _ptr(g_hT), _ptr(g_cT)
         d.g_gx = g_gx.data_ptr()
         with torch.cuda.device(out.device):
@@ -1220,18 +1239,7 @@ class LSTMRecurrenceFunction(torch.autograd.Function):
                 _lib.check(lib.p2c_lstm_steps_bwd(ctypes.byref(d), ws.data_ptr(), _stream()), 'p2c_lstm_steps_bwd')
             else:
                 _lib.check(lib.p2c_lstm_rec_bwd(ctypes.byref(d), _stream()), 'p2c_lstm_rec_bwd')
-        g_w = None
-        if ctx.needs_input_grad[3]:       # dW_hh = sum_t dgates[t]^T h[t-1] over all (t, b) (K12)
-            sink = _sink(w_hh)
-            g_w, acc = sink, sink is not None
-            if T > 1:
-                g_w, acc = atb(g_gx[1:].reshape(-1, 4 * H), out[:-1].reshape(-1, H), out=g_w, accumulate=acc)[0], True
-            if not zero:                  # the t = 0 term meets the initial state (zero state: no contribution)
-                g_w = atb(g_gx[0], h0, out=g_w, accumulate=acc)[0]
-            if g_w is None:
-                g_w = torch.zeros_like(w_hh)
-            if sink is not None:
-                g_w = None                # already added to w_hh.grad
+        g_w = _recurrent_weight_grad(g_gx, out, h0, w_hh, zero) if ctx.needs_input_grad[3] else None
         return g_gx, g_h0, g_c0, g_w
 
 
@@ -1270,8 +1278,8 @@ def lstm_layer(x: Tensor, h0: Optional[Tensor], c0: Optional[Tensor], w_ih: Tens
 # GRU layer: library GEMM for the input projection + one HIP launch per time step for the recurrence (K23)
 # ----------------------------------------------------------------------------------------------------------------------
 def gru_steps_supported(hidden_size: int) -> bool:
-    """The widths of the GRU recurrence (K23, p2c_gru_steps_*): any 1 <= H <= 1024."""
-    return 1 <= hidden_size <= 1024
+    """The widths of the GRU recurrence (K23, p2c_gru_steps_*): any 1 <= H <= REC_STEPS_MAX_HIDDEN."""
+    return 1 <= hidden_size <= REC_STEPS_MAX_HIDDEN
 
 
 class GRURecurrenceFunction(torch.autograd.Function):
@@ -1292,7 +1300,7 @@ class GRURecurrenceFunction(torch.autograd.Function):
         if G != 3 * H or w_hh.shape[0] != 3 * H or (not ctx.zero_state and h0.shape != (B, H)) or (ctx.has_bias and b_hh.shape != (3 * H,)):
             raise RuntimeError(f'inconsistent GRU shapes: gx {tuple(gx.shape)}, w_hh {tuple(w_hh.shape)}, h0 {tuple(h0.shape)}')
         if not gru_steps_supported(H):
-            raise RuntimeError(f'hidden size {H} is not supported by the HIP GRU recurrence (any 1 ... 1024)')
+            raise RuntimeError(f'hidden size {H} is not supported by the HIP GRU recurrence (any 1 ... {REC_STEPS_MAX_HIDDEN})')
         f32 = dict(dtype=torch.float32, device=gx.device)
         out, hT, acts = torch.empty(T, B, H, **f32), torch.empty(B, H, **f32), torch.empty(T, B, 4 * H, **f32)
         d = _lib.GruDesc()
@@ -1323,25 +1331,14 @@ class GRURecurrenceFunction(torch.autograd.Function):
         if not zero:
             g_h0 = torch.empty(B, H, **f32)
             d.h0, d.g_h0 = h0.data_ptr(), g_h0.data_ptr()
-        g_out = None if g_out is None else _require_device(g_out, 'grad out')      # (locals: the copies outlive the launch)
-        g_hT = None if g_hT is None else _require_device(g_hT, 'grad hT')
+        g_out, g_hT = _dense_grad(g_out, 'grad out'), _dense_grad(g_hT, 'grad hT')
         d.g_out, d.g_hT = _ptr(g_out), _ptr(g_hT)
         d.g_gx, d.g_gh = g_gx.data_ptr(), g_gh.data_ptr()
         with torch.cuda.device(out.device):
             ws = torch.empty(lib.p2c_gru_steps_workspace_floats(B, H), **f32)
             _lib.check(lib.p2c_gru_steps_bwd(ctypes.byref(d), ws.data_ptr(), _stream()), 'p2c_gru_steps_bwd')
-        g_w = g_b = None
-        if ctx.needs_input_grad[2]:       # dW_hh = sum_t g_gh[t]^T h[t-1] over all (t, b) (K12)
-            sink = _sink(w_hh)
-            g_w, acc = sink, sink is not None
-            if T > 1:
-                g_w, acc = atb(g_gh[1:].reshape(-1, 3 * H), out[:-1].reshape(-1, H), out=g_w, accumulate=acc)[0], True
-            if not zero:                  # the t = 0 term meets the initial state (zero state: no contribution)
-                g_w = atb(g_gh[0], h0, out=g_w, accumulate=acc)[0]
-            if g_w is None:
-                g_w = torch.zeros_like(w_hh)
-            if sink is not None:
-                g_w = None                # already added to w_hh.grad
+        g_w = _recurrent_weight_grad(g_gh, out, h0, w_hh, zero) if ctx.needs_input_grad[2] else None
+        g_b = None
         if ctx.has_bias and ctx.needs_input_grad[3]:      # db_hh = sum over all (t, b) of g_gh, t = 0 included
             g_b = column_sums(g_gh.view(-1, 3 * H))
             sink = _sink(ctx.bias_param)
