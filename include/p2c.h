@@ -1011,6 +1011,47 @@ typedef struct p2c_lift_desc {
 P2C_API int p2c_lift_supported(const p2c_lift_desc *desc);   /* 1 = the model geometry, kind and precision the kernel covers */
 P2C_API int p2c_lift_fwd(const p2c_lift_desc *desc, void *stream);
 
+/* ---- K33: decoded video clips -> the pose-estimation flow's input frames (csrc/p2c_frames.hip) --------------------------------
+ * What the reference does per clip on the host (data/base/mixins/dataset/video_mixin.py:143-184 crop_bbox, a paste per frame;
+ * transforms/video/video_to_resnet.py:14-56: torchvision equalize per frame and channel, an antialiased bilinear resize per
+ * frame, / 255, ImageNet mean / std), for N clips of T frames in two launches behind one memset node.
+ *   src      one packed uint8 device buffer of src_bytes bytes; clip i is a dense (T, H_i, W_i, 3) block at clips[i].offset.
+ *   clips[i] canvas = 0: the frame itself is the image (vh, vw) = (H, W). canvas > 0: the image is the canvas x canvas zero square
+ *            onto which extract_bbox_from_frame pastes the frame around centres[(i T + t)] = (x, y), half = canvas / 2; the
+ *            canvas is never formed. (out_h, out_w): the size written; equal to (vh, vw) means no resampling.
+ *   centres  (N T, 2) int32 on the device (the host rounds the bboxes; the kernel sees no float bbox); NULL when no clip crops.
+ *   workspace p2c_clip_frames_workspace_bytes(N T) bytes, 4-byte aligned: (N T, 3, 256) int32 level counts, zeroed by the call.
+ *   out      fp32, clip after clip, each (T, 3, out_h, out_w): ((lut[level] resampled, rounded half-even) / 255 - mean_c) / std_c.
+ * Launch A counts the levels of each frame's pasted window (LDS atomics, then int32 global atomics: exact in any order); the zero
+ * padding is added to bin 0 analytically. Launch B rebuilds the three look-up tables of its frame per workgroup (step = (pixels -
+ * count of the last non-empty bin) / 255; step = 0 leaves the channel unchanged; lut[0] = 0, lut[v] = min((cum[v-1] + step / 2) /
+ * step, 255)) and writes one output tile: horizontal taps, LDS, vertical taps. Taps follow torch's antialiased bilinear
+ * interpolate (align_corners = False): scale = in / out, support = max(scale, 1), centre = scale (i + 0.5), window
+ * [int(centre - support + 0.5), int(centre + support + 0.5)) clipped to the image, triangle weights normalised by their sum; the
+ * geometry is formed in fp64, the weights and sums in fp32. Every output element has one writer: two runs give the same bits.
+ * 1 <= N <= P2C_FRAMES_MAX_CLIPS, T >= 1, 1 <= H, W, canvas <= 8192, 1 <= out_h, out_w <= 8192: P2C_E_SHAPE otherwise, and for a
+ * clip block that does not lie inside src_bytes; P2C_E_NULL for a missing pointer; both before any launch. No host sync. */
+#define P2C_FRAMES_MAX_CLIPS 64
+#define P2C_FRAMES_MAX_SIDE 8192
+typedef struct p2c_clip_frames_clip {
+  int64_t offset;
+  int32_t H, W;
+  int32_t canvas;
+  int32_t out_h, out_w;
+  int32_t reserved;
+} p2c_clip_frames_clip;
+typedef struct p2c_clip_frames_desc {
+  int32_t N, T;
+  int64_t src_bytes;
+  const uint8_t *src;
+  const int32_t *centres;
+  int32_t *workspace;
+  float *out;
+  p2c_clip_frames_clip clips[P2C_FRAMES_MAX_CLIPS];
+} p2c_clip_frames_desc;
+P2C_API int64_t p2c_clip_frames_workspace_bytes(int64_t frames);
+P2C_API int p2c_clip_frames_fwd(const p2c_clip_frames_desc *desc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

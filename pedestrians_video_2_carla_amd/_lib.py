@@ -219,6 +219,20 @@ class HeatmapKeypointsDesc(ctypes.Structure):
                 ('maps', _f32p), ('out', _f32p)]
 
 
+P2C_FRAMES_MAX_CLIPS, P2C_FRAMES_MAX_SIDE = 64, 8192
+
+
+class ClipFramesClip(ctypes.Structure):
+    """p2c_clip_frames_clip (include/p2c.h)."""
+    _fields_ = [('offset', _i64), ('H', _i32), ('W', _i32), ('canvas', _i32), ('out_h', _i32), ('out_w', _i32), ('reserved', _i32)]
+
+
+class ClipFramesDesc(ctypes.Structure):
+    """p2c_clip_frames_desc (include/p2c.h)."""
+    _fields_ = [('N', _i32), ('T', _i32), ('src_bytes', _i64), ('src', _vp), ('centres', _vp), ('workspace', _vp), ('out', _f32p),
+                ('clips', ClipFramesClip * P2C_FRAMES_MAX_CLIPS)]
+
+
 SYMBOLS = {
     'p2c_version': (ctypes.c_char_p, []),
     'p2c_pose_head_workspace_floats': (_i64, [_i32]),
@@ -330,6 +344,8 @@ SYMBOLS = {
     'p2c_carla_pose_inv': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     'p2c_lift_supported': (ctypes.c_int, [ctypes.POINTER(LiftDesc)]),
     'p2c_lift_fwd': (ctypes.c_int, [ctypes.POINTER(LiftDesc), _vp]),
+    'p2c_clip_frames_workspace_bytes': (_i64, [_i64]),
+    'p2c_clip_frames_fwd': (ctypes.c_int, [ctypes.POINTER(ClipFramesDesc), _vp]),
 }
 
 _lib = None

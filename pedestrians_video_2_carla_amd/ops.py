@@ -3531,3 +3531,137 @@ def _lift_desc(x, weights, biases, skel_type, kind, image, image_is_current, wor
     d.world_loc, d.world_rot, d.initial_rel_rot = _ptr(world_loc), _ptr(world_rot), _ptr(initial_rel_rot)
     d.bones, d.root, d.final_rel_rot, d.out_relative_pose_rot = bones.data_ptr(), _ptr(root), _ptr(final_rel_rot), _ptr(rot)
     return d
+
+
+# ---- K33: decoded video clips -> the pose-estimation flow's input frames (csrc/p2c_frames.hip) ---------------------------------
+FRAMES_MAX_TARGET = 1024             # the largest target size K33 is dispatched for
+
+
+def frames_framework() -> bool:
+    """P2C_FRAMES_FRAMEWORK=1: ``clip_frames`` runs the tensor definition (data/base/video.py) on the clips' device (the comparison
+    arm of tools/bench_frames.py)."""
+    return os.environ.get('P2C_FRAMES_FRAMEWORK', '0') == '1'
+
+
+@dataclass
+class PackedClips:
+    """N decoded clips in one uint8 buffer: clip i is the dense (T, H_i, W_i, 3) block at ``offsets[i]`` (bytes)."""
+    buffer: Tensor
+    offsets: Tuple[int, ...]
+    shapes: Tuple[Tuple[int, int, int], ...]
+
+    def __len__(self):
+        return len(self.shapes)
+
+    def clip(self, i: int) -> Tensor:
+        T, H, W = self.shapes[i]
+        return self.buffer[self.offsets[i]:self.offsets[i] + T * H * W * 3].view(T, H, W, 3)
+
+
+def pack_clips(clips: Sequence[Tensor]) -> PackedClips:
+    """One buffer from a list of uint8 (T, H_i, W_i, 3) tensors on one device (a single clip that is already dense is not copied)."""
+    shapes, offsets, at = [], [], 0
+    for c in clips:
+        if c.ndim != 4 or c.shape[3] != 3 or c.dtype != torch.uint8:
+            raise RuntimeError(f'clip_frames: a clip is uint8 (T,H,W,3), got {c.dtype} {tuple(c.shape)}')
+        shapes.append(tuple(int(v) for v in c.shape[:3]))
+        offsets.append(at)
+        at += c.numel()
+    buffer = clips[0].contiguous().view(-1) if len(clips) == 1 else torch.cat([c.reshape(-1) for c in clips])
+    return PackedClips(buffer, tuple(offsets), tuple(shapes))
+
+
+def _frames_sizes(packed: PackedClips, target_size: int, canvas):
+    """Per clip: the (height, width) that is resized -- the canvas under the crop -- and the size written."""
+    from pedestrians_video_2_carla_amd.data.base.video import resized_size
+    src = [(int(canvas[i]),) * 2 if canvas is not None else (H, W) for i, (_, H, W) in enumerate(packed.shapes)]
+    return src, [resized_size(h, w, target_size) for h, w in src]
+
+
+def clip_frames_supported(clips, target_size: int, canvas=None) -> bool:
+    """What K33 covers: uint8 clips on the device, frame and canvas sides up to 8 192 (int32 level counts), a target size in
+    [1, 1024]; everything else, and ``P2C_FRAMES_FRAMEWORK=1``, is the tensor path."""
+    packed = clips if isinstance(clips, PackedClips) else None
+    tensors = [packed.buffer] if packed is not None else list(clips)
+    if frames_framework() or not all(isinstance(t, Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.device == tensors[0].device
+                                     for t in tensors):
+        return False
+    shapes = packed.shapes if packed is not None else [tuple(t.shape[:3]) for t in tensors]
+    side = max(max(s[1], s[2]) for s in shapes)
+    if canvas is not None:
+        side = max(side, max(int(c) for c in canvas))
+    return 1 <= int(target_size) <= FRAMES_MAX_TARGET and side <= _lib.P2C_FRAMES_MAX_SIDE
+
+
+def _clip_frames_tensor(packed: PackedClips, target_size: int, centres, canvas) -> Tensor:
+    """The definition: per clip the reference's paste (around the given integer centres), then ``VideoToResNet``."""
+    from pedestrians_video_2_carla_amd.data.base.video import VideoToResNet, extract_bbox_from_frame
+    to_resnet, out = VideoToResNet(target_size), []
+    if isinstance(centres, Tensor):
+        T = packed.shapes[0][0]
+        centres = centres.detach().cpu().numpy().reshape(len(packed), T, 2)
+    for i in range(len(packed)):
+        clip = packed.clip(i)
+        if canvas is not None:
+            c, (T, H, W) = int(canvas[i]), packed.shapes[i]
+            pasted = clip.new_zeros((T, c, c, 3))
+            for t in range(T):
+                extract_bbox_from_frame(pasted[t], clip[t], (c // 2, c // 2), centres[i][t], (W, H))
+            clip = pasted
+        out.append(to_resnet(clip))
+    return torch.stack(out)
+
+
+def clip_frames(clips, target_size: int, centres=None, canvas=None) -> Tensor:
+    """Decoded clips -> the pose-estimation flow's frames (N,T,3,h,w) fp32: the reference's ``crop_bbox`` paste (when ``canvas`` is
+    given), ``equalize`` per frame and channel, the antialiased bilinear resize of ``VideoToResNet`` and the ImageNet
+    normalisation -- K33, two launches for the whole batch; the canvas, the equalized clip and the float image are never formed.
+
+    ``clips``: a list of uint8 (T, H_i, W_i, 3) tensors or a ``PackedClips``. ``canvas``: per clip the canvas size of
+    ``data.base.video.crop_geometry`` (None: no crop); ``centres``: with it, per clip the (T,2) integer (x, y) centres -- a list
+    of host arrays (one small upload) or an int32 device tensor (N,T,2) (nothing is copied: capturable). All clips must have the
+    same T and resize to the same (h, w). Host clips, sizes ``clip_frames_supported`` refuses and ``P2C_FRAMES_FRAMEWORK=1`` run
+    the tensor definition on the clips' device."""
+    import numpy as np
+    packed = clips if isinstance(clips, PackedClips) else pack_clips(list(clips))
+    N = len(packed)
+    if N == 0:
+        raise RuntimeError('clip_frames: no clips')
+    if (canvas is None) != (centres is None) or (canvas is not None and len(canvas) != N):
+        raise RuntimeError('clip_frames: canvas and centres come together, one entry per clip')
+    T = packed.shapes[0][0]
+    if T < 1 or any(s[0] != T for s in packed.shapes):
+        raise RuntimeError(f'clip_frames: every clip needs the same T >= 1, got {[s[0] for s in packed.shapes]}')
+    _, sizes = _frames_sizes(packed, target_size, canvas)
+    if len(set(sizes)) != 1:
+        raise RuntimeError(f'clip_frames: the clips resize to different sizes {sorted(set(sizes))}')
+    if not clip_frames_supported(packed, target_size, canvas):
+        return _clip_frames_tensor(packed, target_size, centres, canvas)
+    lib = _lib.lib()
+    dev = packed.buffer.device
+    if canvas is None:
+        centres_dev = None
+    elif isinstance(centres, Tensor):
+        if not centres.is_cuda or centres.dtype != torch.int32 or centres.numel() != N * T * 2:
+            raise RuntimeError('clip_frames: a tensor of centres is int32 (N,T,2) on the device')
+        centres_dev = centres.contiguous()
+    else:
+        host = np.ascontiguousarray(np.stack([np.asarray(c) for c in centres]).reshape(N, T, 2).clip(-2 ** 30, 2 ** 30), dtype=np.int32)
+        centres_dev = torch.from_numpy(host).to(dev)
+    h, w = sizes[0]
+    out = torch.empty(N, T, 3, h, w, dtype=torch.float32, device=dev)
+    workspace = torch.empty(lib.p2c_clip_frames_workspace_bytes(min(N, _lib.P2C_FRAMES_MAX_CLIPS) * T) // 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        for i0 in range(0, N, _lib.P2C_FRAMES_MAX_CLIPS):              # the per-clip table travels in the kernel arguments
+            n = min(_lib.P2C_FRAMES_MAX_CLIPS, N - i0)
+            d = _lib.ClipFramesDesc()
+            d.N, d.T, d.src_bytes, d.src = n, T, packed.buffer.numel(), packed.buffer.data_ptr()
+            d.centres = None if centres_dev is None else centres_dev.data_ptr() + i0 * T * 2 * 4
+            d.workspace, d.out = workspace.data_ptr(), out[i0].data_ptr()
+            for k in range(n):
+                _, H, W = packed.shapes[i0 + k]
+                clip = d.clips[k]
+                clip.offset, clip.H, clip.W, clip.out_h, clip.out_w = packed.offsets[i0 + k], H, W, h, w
+                clip.canvas = 0 if canvas is None else int(canvas[i0 + k])
+            _lib.check(lib.p2c_clip_frames_fwd(ctypes.byref(d), _stream()), 'p2c_clip_frames_fwd')
+    return out
