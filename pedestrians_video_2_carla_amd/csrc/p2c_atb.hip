@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 
 namespace p2c_atb_impl {
 
@@ -243,8 +244,7 @@ extern "C" int p2c_atb_scaled(const float *A, int64_t lda, const float *B, int64
   a.ks = slices_for(a.tiles, K);
   hipLaunchKernelGGL(atb_kernel, dim3((unsigned)launch_blocks(a)), dim3(64 * WAVES), 0, (hipStream_t)stream, a);
   hipLaunchKernelGGL(atb_finish_kernel, dim3((unsigned)a.tiles), dim3(256), 0, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_atb(const float *A, int64_t lda, const float *B, int64_t ldb, int64_t K, int32_t M, int32_t N, float *C,
@@ -291,6 +291,5 @@ extern "C" int p2c_atb_group(const p2c_atb_problem *p, int32_t n, float *workspa
   if (rc) return rc;
   hipLaunchKernelGGL(atb_group_kernel, dim3((unsigned)g.first[n]), dim3(64 * WAVES), 0, (hipStream_t)stream, g);
   hipLaunchKernelGGL(atb_group_finish_kernel, dim3((unsigned)g.ffirst[n]), dim3(256), 0, (hipStream_t)stream, g);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 
 namespace p2c_attn {
 
@@ -471,9 +472,6 @@ static int check(const Args &a, bool bwd, size_t *lds) {
 }
 
 // copy_rows, vec_contract and the narrow stores move 16 bytes at a time straight from / to global memory
-static bool aligned16(const void *a, const void *b, const void *c = nullptr) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
-}
 
 #define P2C_ATTN_ROW(K, F) {(const void *)K<F, 16>, (const void *)K<F, 32>, (const void *)K<F, 64>}
 static const void *const fwd_kernels[4][3] = {P2C_ATTN_ROW(attn_fwd_kernel, F_GENERIC), P2C_ATTN_ROW(attn_fwd_kernel, F_NARROW4),
@@ -504,7 +502,7 @@ extern "C" int p2c_attn_small_fwd(const float *qkv, float *out, float scale, int
                                   void *stream) {
   using namespace p2c_attn;
   if (!qkv || !out) return P2C_E_NULL;
-  if (!aligned16(qkv, out)) return P2C_E_SHAPE;
+  if (!p2c_host::aligned16(qkv, out)) return P2C_E_SHAPE;
   Args a{};
   a.qkv = qkv, a.out = out, a.scale = scale, a.S = S, a.N = N, a.Hh = heads, a.D = head_dim;
   size_t lds;
@@ -518,15 +516,14 @@ extern "C" int p2c_attn_small_fwd(const float *qkv, float *out, float scale, int
   const void *kernel = fwd_kernels[family(N, head_dim)][N <= 16 ? 0 : N <= 32 ? 1 : 2];
   void *kargs[] = {&a};
   (void)hipLaunchKernel(kernel, dim3((unsigned)grid), dim3(256), kargs, lds, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_attn_small_bwd(const float *qkv, const float *g_out, float *g_qkv, float scale, int32_t S, int32_t N,
                                   int32_t heads, int32_t head_dim, void *stream) {
   using namespace p2c_attn;
   if (!qkv || !g_out || !g_qkv) return P2C_E_NULL;
-  if (!aligned16(qkv, g_out, g_qkv)) return P2C_E_SHAPE;
+  if (!p2c_host::aligned16(qkv, g_out, g_qkv)) return P2C_E_SHAPE;
   Args a{};
   a.qkv = qkv, a.g_out = g_out, a.g_qkv = g_qkv, a.scale = scale, a.S = S, a.N = N, a.Hh = heads, a.D = head_dim;
   size_t lds;
@@ -540,8 +537,7 @@ extern "C" int p2c_attn_small_bwd(const float *qkv, const float *g_out, float *g
   const void *kernel = bwd_kernels[family(N, head_dim)][N <= 16 ? 0 : N <= 32 ? 1 : 2];
   void *kargs[] = {&a};
   (void)hipLaunchKernel(kernel, dim3((unsigned)grid), dim3(256), kargs, lds, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 #ifdef P2C_ATTN_TRACE

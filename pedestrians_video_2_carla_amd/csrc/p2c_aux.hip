@@ -6,9 +6,14 @@
 #include <math.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
+#include "p2c_lane_dev.h"
 
 namespace p2c_aux {
 
+using p2c_lane::xor_max;
+using p2c_lane::xor_min;
+using p2c_lane::xor_sum;
 constexpr int MAXJ = 64;
 
 struct NormArgs {
@@ -22,25 +27,6 @@ struct NormArgs {
   int32_t hips_idx[2], neck_idx[2];
   float near_zero;
 };
-
-template <int G>
-__device__ __forceinline__ float gsum(float v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-template <int G>
-__device__ __forceinline__ float gmin(float v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
-  return v;
-}
-template <int G>
-__device__ __forceinline__ float gmax(float v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-  return v;
-}
 
 // Normalizer.__call__ (transforms/pose/normalization/normalizer.py:20-41) with the extractors of the same package:
 // hips_neck_extractor.py:6-13, bbox_extractor.py:6-18 (+ utils/tensors.py:12-26), hips_neck_bbox_fallback_extractor.py:20-40.
@@ -90,8 +76,8 @@ __global__ __launch_bounds__(256) void normalize_kernel(const NormArgs a) {
   if (__any(need_bb)) {  // dim == 2 guaranteed by the host wrapper
     missing = !active || ((p[0] < a.near_zero) && (p[1] < a.near_zero));
     const float inf = __builtin_inff();
-    mn[0] = gmin<G>(missing ? inf : p[0]), mn[1] = gmin<G>(missing ? inf : p[1]);
-    mx[0] = gmax<G>(missing ? -inf : p[0]), mx[1] = gmax<G>(missing ? -inf : p[1]);
+    mn[0] = xor_min<G>(missing ? inf : p[0]), mn[1] = xor_min<G>(missing ? inf : p[1]);
+    mx[0] = xor_max<G>(missing ? -inf : p[0]), mx[1] = xor_max<G>(missing ? -inf : p[1]);
     float cu = 0.5f * (mn[0] + mx[0]), cv = 0.5f * (mn[1] + mx[1]);
     float dx = cu - cu, dy = fminf(mn[1], mx[1]) - cv;
     bb_scale = sqrtf(fmaf(dx, dx, dy * dy));
@@ -149,8 +135,8 @@ __global__ __launch_bounds__(256) void normalize_kernel(const NormArgs a) {
     gp[c] = ok ? g[c] * inv : 0.f;
     Cs_l = fmaf(gp[c], o[c], Cs_l);
   }
-  for (int c = 0; c < dim; ++c) A[c] = gsum<G>(gp[c]);
-  float g_scale = -gsum<G>(Cs_l);
+  for (int c = 0; c < dim; ++c) A[c] = xor_sum<G>(gp[c]);
+  float g_scale = -xor_sum<G>(Cs_l);
   float gs[3] = {-A[0], -A[1], -A[2]};
   float g_bbs = 0.f;
   if (tr == P2C_TRANSFORM_BBOX) {
@@ -229,7 +215,7 @@ __global__ __launch_bounds__(256) void loss2d_fwd_kernel(const Loss2dArgs a, flo
     }
   }
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64), c += __shfl_xor(c, d, 64);
+  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64), c += __shfl_xor(c, d, 64);   // (two sums, one loop: their shuffles alternate)
   if ((threadIdx.x & 63) == 0) {
     int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     partials[wave * 2 + 0] = s, partials[wave * 2 + 1] = c;
@@ -343,8 +329,7 @@ static int norm_launch(bool bwd, const float *x, const float *grad_out, float *o
     if (bwd) hipLaunchKernelGGL((normalize_kernel<64, true>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((normalize_kernel<64, false>), grid, block, 0, stream, a);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_normalize_fwd(const float *x, float *out, float *shift, float *scale, int64_t N, int32_t Jn, int32_t C,
@@ -390,8 +375,7 @@ extern "C" int p2c_loss2d_fwd(const float *pred, const float *gt, int64_t N, int
   unsigned grid = stream_grid(N * K);
   hipLaunchKernelGGL(loss2d_fwd_kernel, dim3(grid), dim3(256), 0, stream, a, partials);
   hipLaunchKernelGGL(loss2d_finalize, dim3(1), dim3(256), 0, stream, (const float *)partials, (int)(grid * 4), loss_sums, loss);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_loss2d_bwd(const float *pred, const float *gt, int64_t N, int32_t Jp, int32_t Cp, int32_t Jg, int32_t Cg,
@@ -404,8 +388,7 @@ extern "C" int p2c_loss2d_bwd(const float *pred, const float *gt, int64_t N, int
   if (!loss_sums || !grad_loss || !grad_pred) return P2C_E_NULL;
   hipStream_t stream = (hipStream_t)stream_;
   hipLaunchKernelGGL(loss2d_bwd_kernel, dim3(stream_grid(N * Jp)), dim3(256), 0, stream, a, loss_sums, grad_loss, grad_pred);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_remap_nodes(const float *src, float *dst, int64_t N, int32_t Jsrc, int32_t Jdst, int32_t C, int32_t K,
@@ -421,8 +404,7 @@ extern "C" int p2c_remap_nodes(const float *src, float *dst, int64_t N, int32_t 
   }
   if (N == 0) return 0;
   hipLaunchKernelGGL(remap_kernel, dim3(stream_grid(N * Jdst * C)), dim3(256), 0, (hipStream_t)stream_, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 // ---- grouped copy: the tensors of a new batch into the static buffers of a captured step, ONE launch ------------------------
@@ -476,8 +458,7 @@ extern "C" int p2c_copy_group(const void *const *src, void *const *dst, const in
   }
   if (a.n == 0) return 0;
   hipLaunchKernelGGL(copy_group_kernel, dim3((unsigned)a.first[a.n]), dim3(256), 0, (hipStream_t)stream_, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 // ---- inspection: what a captured HIP graph holds --------------------------------------------------------------------------
@@ -521,8 +502,7 @@ extern "C" int p2c_debug_poison_lds(void *stream) {
   hipError_t e = hipFuncSetAttribute((const void *)p2c_aux::poison_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(p2c_aux::poison_lds_kernel, dim3(256 * 8), dim3(1024), bytes, (hipStream_t)stream, bytes / 4);
-  e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 
@@ -550,11 +530,10 @@ __global__ __launch_bounds__(256) void frame_mean_kernel(const float *x, const f
 extern "C" int p2c_frame_mean_fwd(const float *x, const float *w, const float *bias, float *out, int64_t B, int32_t F, int32_t C,
                                   void *stream) {
   if (!x || !w || !out) return P2C_E_NULL;
-  if (B < 0 || F < 1 || C < 4 || (C & 3) || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15)) return P2C_E_SHAPE;
+  if (B < 0 || F < 1 || C < 4 || (C & 3) || !p2c_host::aligned16(x, out)) return P2C_E_SHAPE;
   if (B == 0) return 0;
   const int64_t n = B * (C >> 2);
   const unsigned grid = (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
   hipLaunchKernelGGL(p2c_aux::frame_mean_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, w, bias, out, B, F, C);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

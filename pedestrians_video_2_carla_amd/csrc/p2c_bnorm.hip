@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 #include "p2c_rec_dev.h"
 
 namespace p2c_bnorm {
@@ -353,16 +354,9 @@ __global__ __launch_bounds__(THREADS) void apply_bwd_kernel(Args a) {
 }
 
 inline bool shape_ok(int64_t N, int32_t C) { return N >= 1 && C >= 1 && N * (int64_t)C < ((int64_t)1 << 31); }
-inline bool a16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 inline void set_drop(Args &a, const p2c_bnorm_desc *d) {
-  a.drop = DropRng{};
-  if (d->drop_state && d->drop_p > 0.f) {
-    a.drop.state = static_cast<int32_t *>(d->drop_state);
-    a.drop.thresh = d->drop_p >= 1.f ? 0xFFFFFFFFu : (uint32_t)((double)d->drop_p * 4294967296.0);
-    a.drop.scale = d->drop_p >= 1.f ? 0.f : 1.f / (1.f - d->drop_p);
-    a.drop.site = d->drop_site;
-  }
+  a.drop = (d->drop_state && d->drop_p > 0.f) ? DropRng(d->drop_state, d->drop_p, d->drop_site) : DropRng{};
 }
 
 #define P2C_BN_LAUNCH(kernel, vec, grid)                                                                                  \
@@ -389,7 +383,7 @@ extern "C" int p2c_bnorm_fwd(const p2c_bnorm_desc *d, float *workspace, void *st
   if (!d->y || !d->gamma || !d->beta || !d->z || !d->mean || !d->rstd) return P2C_E_NULL;
   if (d->training ? !workspace : (!d->running_mean || !d->running_var)) return P2C_E_NULL;
   if ((d->running_mean == nullptr) != (d->running_var == nullptr)) return P2C_E_NULL;
-  const bool vec4 = d->C % 4 == 0 && a16(d->y) && a16(d->z) && (!d->residual || a16(d->residual));
+  const bool vec4 = d->C % 4 == 0 && p2c_host::aligned16(d->y, d->z, d->residual);
   const Plan p = plan_for(d->N, d->C, vec4);
   Args a{};
   a.y = d->y, a.gamma = d->gamma, a.beta = d->beta, a.residual = d->residual, a.z = d->z;
@@ -408,8 +402,7 @@ extern "C" int p2c_bnorm_fwd(const p2c_bnorm_desc *d, float *workspace, void *st
     a.drop = DropRng{};
   }
   P2C_BN_LAUNCH(apply_fwd_kernel, p.vec, grid);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_bnorm_bwd(const p2c_bnorm_desc *d, float *workspace, void *stream) {
@@ -418,7 +411,7 @@ extern "C" int p2c_bnorm_bwd(const p2c_bnorm_desc *d, float *workspace, void *st
   if (!shape_ok(d->N, d->C) || (d->training && d->N < 2)) return P2C_E_SHAPE;
   if (!d->y || !d->gamma || !d->beta || !d->mean || !d->rstd || !d->g_z || !d->g_y || !d->g_gamma || !d->g_beta || !workspace)
     return P2C_E_NULL;
-  const bool vec4 = d->C % 4 == 0 && a16(d->y) && a16(d->g_z) && a16(d->g_y);
+  const bool vec4 = d->C % 4 == 0 && p2c_host::aligned16(d->y, d->g_z, d->g_y);
   const Plan p = plan_for(d->N, d->C, vec4);
   Args a{};
   a.y = d->y, a.gamma = d->gamma, a.beta = d->beta, a.g_z = d->g_z, a.g_y = d->g_y, a.g_gamma = d->g_gamma, a.g_beta = d->g_beta;
@@ -431,6 +424,5 @@ extern "C" int p2c_bnorm_bwd(const p2c_bnorm_desc *d, float *workspace, void *st
   P2C_BN_LAUNCH(reduce_bwd_kernel, p.vec, grid);
   hipLaunchKernelGGL(reduce_finalize_kernel, dim3((unsigned)((d->C + 63) / 64)), dim3(THREADS), 0, (hipStream_t)stream, a);
   P2C_BN_LAUNCH(apply_bwd_kernel, p.vec, grid);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

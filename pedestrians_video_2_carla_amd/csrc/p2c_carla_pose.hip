@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 
 #include "p2c_carla_dev.h"   // kDeg, kRad, clamp_unit, carla_row: shared with K32 (p2c_lift.hip)
 
@@ -114,8 +115,7 @@ extern "C" int p2c_carla_pose_fwd(const float *rel_loc, const float *rel_rot, co
   a.n_bones = N * J;
   a.n_total = a.n_bones + (world_loc ? N : 0);
   hipLaunchKernelGGL(carla_pose_fwd_kernel, dim3(blocks_for(a.n_total, max_blocks)), dim3(kThreads), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_carla_pose_inv(const float *bones, float *loc, float *rot, int64_t N, int32_t J, int32_t max_blocks,
@@ -128,6 +128,5 @@ extern "C" int p2c_carla_pose_inv(const float *bones, float *loc, float *rot, in
   a.bones = bones, a.loc = loc, a.rot = rot;
   a.n_bones = N * J;
   hipLaunchKernelGGL(carla_pose_inv_kernel, dim3(blocks_for(a.n_bones, max_blocks)), dim3(kThreads), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

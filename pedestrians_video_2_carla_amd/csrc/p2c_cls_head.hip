@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 
 namespace p2c_cls {
 
@@ -113,6 +114,5 @@ extern "C" int p2c_cls_head(const float *logits, const int64_t *targets, int64_t
   if ((B > 0 && (!logits || !targets)) || (!count_only && !loss) || (count_only && !confusion)) return P2C_E_NULL;
   hipLaunchKernelGGL(p2c_cls::cls_head_kernel, dim3(1), dim3(p2c_cls::NT), 0, (hipStream_t)stream, logits, targets, B,
                      (int)C, binary ? 1 : 0, count_only ? 1 : 0, loss, g_logits, confusion);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

@@ -24,6 +24,8 @@
 #include <math.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
+#include "p2c_lane_dev.h"
 
 namespace p2c_collate {
 
@@ -83,18 +85,8 @@ struct View {
   int32_t perm_j, inv_j;
 };
 
-template <int G>
-__device__ __forceinline__ float gmin(float v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
-  return v;
-}
-template <int G>
-__device__ __forceinline__ float gmax(float v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-  return v;
-}
+using p2c_lane::xor_max;
+using p2c_lane::xor_min;
 __device__ __forceinline__ float finite_or_zero(float v) { return isfinite(v) ? v : 0.f; }   // nan_to_zero
 
 // Normalizer.__call__ (normalizer.py:20-41), dim = 2, for the frame of this lane group: (x, y[, conf]) -> normalised
@@ -125,8 +117,8 @@ __device__ __forceinline__ void normalise(const View &v, float near_zero, int ba
   if (__any(tr == P2C_TRANSFORM_BBOX || use_bb)) {
     const bool missing = !active || (x < near_zero && y < near_zero);
     const float inf = __builtin_inff();
-    const float mn0 = gmin<G>(missing ? inf : x), mn1 = gmin<G>(missing ? inf : y);
-    const float mx0 = gmax<G>(missing ? -inf : x), mx1 = gmax<G>(missing ? -inf : y);
+    const float mn0 = xor_min<G>(missing ? inf : x), mn1 = xor_min<G>(missing ? inf : y);
+    const float mx0 = xor_max<G>(missing ? -inf : x), mx1 = xor_max<G>(missing ? -inf : y);
     const float cu = 0.5f * (mn0 + mx0), cv = 0.5f * (mn1 + mx1);
     const float dx = cu - cu, dy = fminf(mn1, mx1) - cv;
     const float bb_scale = sqrtf(fmaf(dx, dx, dy * dy));
@@ -184,8 +176,8 @@ __device__ __forceinline__ void collate_frame(const A &a, const View &v, int j, 
     } else {                                                   // get_bboxes(pose), utils/tensors.py:12-26
       const bool missing = !active || (x < a.near_zero && y < a.near_zero);
       const float inf = __builtin_inff();
-      lo[0] = gmin<G>(missing ? inf : x), lo[1] = gmin<G>(missing ? inf : y);
-      hi[0] = gmax<G>(missing ? -inf : x), hi[1] = gmax<G>(missing ? -inf : y);
+      lo[0] = xor_min<G>(missing ? inf : x), lo[1] = xor_min<G>(missing ? inf : y);
+      hi[0] = xor_max<G>(missing ? -inf : x), hi[1] = xor_max<G>(missing ? -inf : y);
     }
     ctr[0] = (lo[0] + hi[0]) * 0.5f, ctr[1] = (lo[1] + hi[1]) * 0.5f;
   }
@@ -374,8 +366,7 @@ extern "C" int p2c_collate_fwd(const p2c_collate_desc *d, void *stream_) {
   const dim3 block(256), grid((unsigned)((waves + 3) / 4));
   if (G == 32) hipLaunchKernelGGL(collate_kernel<32>, grid, block, 0, (hipStream_t)stream_, a);
   else hipLaunchKernelGGL(collate_kernel<64>, grid, block, 0, (hipStream_t)stream_, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_collate_mixed_fwd(const p2c_collate_mixed_desc *d, void *stream_) {
@@ -443,6 +434,5 @@ extern "C" int p2c_collate_mixed_fwd(const p2c_collate_mixed_desc *d, void *stre
   const dim3 block(256), grid((unsigned)((waves + 3) / 4));
   if (G == 32) hipLaunchKernelGGL(collate_mixed_kernel<32>, grid, block, 0, (hipStream_t)stream_, a);
   else hipLaunchKernelGGL(collate_mixed_kernel<64>, grid, block, 0, (hipStream_t)stream_, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 
 namespace p2c_embed {
 
@@ -163,15 +164,14 @@ extern "C" int p2c_embed_fwd(const float *x, const float *W, const float *b, int
   int rc = fill(a, x, W, b, w_stride, b_stride, B, T, J, C, E, flip);
   if (rc) return rc;
   if (!y) return P2C_E_NULL;
-  if ((reinterpret_cast<uintptr_t>(y) & 15) != 0) return P2C_E_SHAPE;
+  if (!p2c_host::aligned16(y)) return P2C_E_SHAPE;
   if (B == 0) return 0;
   a.y = y;
   const int64_t total = (((int64_t)B * T + ROWS - 1) / ROWS) * J * (E >> 2);
   int64_t blocks = (total + 255) / 256;
   if (blocks > 256 * 16) blocks = 256 * 16;
   hipLaunchKernelGGL(embed_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_embed_bwd(const float *x, const float *gy, int64_t w_stride, int64_t b_stride, float *gW, float *gb,
@@ -185,8 +185,7 @@ extern "C" int p2c_embed_bwd(const float *x, const float *gy, int64_t w_stride, 
   hipLaunchKernelGGL(embed_bwd_partial_kernel, dim3((unsigned)J, (unsigned)a.n_chunks), dim3(256), 0, (hipStream_t)stream, a);
   const int total = J * E * (C + 1);
   hipLaunchKernelGGL(embed_bwd_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 // ---- folded input map (K7a'): embeddings composed with the encoder's first input projection -------------------------------
@@ -341,8 +340,7 @@ extern "C" int p2c_fold_fwd(const float *w_ih, const float *W, const float *b, i
   a.w_ih = w_ih, a.W = W, a.b = b, a.b_ih = b_ih, a.b_hh = b_hh, a.w_eff = w_eff, a.b_eff = b_eff;
   a.w_stride = w_stride, a.b_stride = b_stride, a.G = G, a.J = J, a.E = E, a.C = C;
   hipLaunchKernelGGL(p2c_fold::fold_fwd_kernel, dim3((unsigned)G), dim3(256), (size_t)(J * E + J) * sizeof(float), (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_fold_bwd(const float *w_ih, const float *W, const float *b, int64_t w_stride, int64_t b_stride,
@@ -357,6 +355,5 @@ extern "C" int p2c_fold_bwd(const float *w_ih, const float *W, const float *b, i
   const size_t lds = ((size_t)G * (C + 1) + (size_t)p2c_fold::GG * 64 * (p2c_fold::MAXC + 1)) * sizeof(float);
   if (lds > 60 * 1024) return P2C_E_SHAPE;
   hipLaunchKernelGGL(p2c_fold::fold_bwd_kernel, dim3((unsigned)J), dim3(64 * p2c_fold::GG), lds, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

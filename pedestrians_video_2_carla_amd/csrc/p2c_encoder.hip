@@ -30,32 +30,17 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
+#include "p2c_lane_dev.h"
 #include "p2c_rec_dev.h"
 
 namespace p2c_encoder {
 
+using p2c_lane::xor_max;
+using p2c_lane::xor_sum;
 using p2c_rec::DropRng;
 constexpr int THREADS = 256, WAVES = THREADS / 64, MAXN = 64, PITCH = MAXN + 1;
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-static DropRng make_drop(void *state, float p, int32_t site) {
-  DropRng r{};
-  r.state = static_cast<int32_t *>(state);
-  r.thresh = p >= 1.f ? 0xFFFFFFFFu : (uint32_t)((double)p * 4294967296.0);
-  r.scale = p >= 1.f ? 0.f : 1.f / (1.f - p);
-  r.site = site;
-  return r;
-}
 
 // ---- K20a ------------------------------------------------------------------------------------------------------------------------
 struct AttnArgs {
@@ -80,9 +65,9 @@ __device__ __forceinline__ void probabilities(const AttnArgs &a, const float *q,
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int i = wave; i < N; i += WAVES) {
     const float x = lane < N ? P[i][lane] : -INFINITY;
-    const float mx = wave_max(x);
+    const float mx = xor_max<64>(x);
     const float e = lane < N ? expf(x - mx) : 0.f;
-    const float sum = wave_sum(e);
+    const float sum = xor_sum<64>(e);
     if (lane < N) P[i][lane] = e / sum;
   }
   __syncthreads();
@@ -136,7 +121,7 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_kernel(AttnArgs a) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int i = wave; i < N; i += WAVES) {
     const float pg = lane < N ? P[i][lane] * G[i][lane] : 0.f;
-    const float rd = wave_sum(pg);
+    const float rd = xor_sum<64>(pg);
     if (lane < N) G[i][lane] = P[i][lane] * (G[i][lane] - rd);
   }
   __syncthreads();
@@ -165,18 +150,6 @@ struct NormArgs {
   DropRng drop;
 };
 
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-template <int G>
-__device__ __forceinline__ double group_sum_f64(double v) {
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ float keep_of(const DropRng &d, int64_t r, int D, int col) {
   return d.state ? p2c_rec::drop_value(d, (uint32_t)(r * D + col)) : 1.f;
 }
@@ -208,14 +181,14 @@ __global__ __launch_bounds__(THREADS) void postnorm_fwd_kernel(NormArgs a) {
       if (live && col < D) u[k] = fma((double)a.s[r * D + col], (double)keep_of(a.drop, r, D, col), (double)a.x[r * D + col]);
       s1 += u[k];
     }
-    const double mean = group_sum_f64<G>(s1) * inv_d64;
+    const double mean = xor_sum<G>(s1) * inv_d64;
     float t[KV], q = 0.f;
 #pragma unroll
     for (int k = 0; k < KV; ++k) {
       t[k] = (k * G + l < D) ? (float)(u[k] - mean) : 0.f;
       q = fmaf(t[k], t[k], q);
     }
-    const float rstd = rsqrtf(group_sum<G>(q) * inv_d + a.eps);
+    const float rstd = rsqrtf(xor_sum<G>(q) * inv_d + a.eps);
     if (!live) continue;
 #pragma unroll
     for (int k = 0; k < KV; ++k) {
@@ -257,7 +230,7 @@ __global__ __launch_bounds__(THREADS) void postnorm_bwd_kernel(NormArgs a) {
       u[k] = ok ? fma((double)a.s[r * D + col], (double)keep[k], (double)a.x[r * D + col]) : 0.0;
       s0 += u[k];
     }
-    const double mean = group_sum_f64<G>(s0) * inv_d64;       // (the forward's operations: the same bits)
+    const double mean = xor_sum<G>(s0) * inv_d64;       // (the forward's operations: the same bits)
 #pragma unroll
     for (int k = 0; k < KV; ++k) {
       const int col = k * G + l;
@@ -270,7 +243,7 @@ __global__ __launch_bounds__(THREADS) void postnorm_bwd_kernel(NormArgs a) {
       dg[k] = fmaf(g, xh[k], dg[k]);
       db[k] += g;
     }
-    const float m1 = group_sum<G>(s1) * inv_d, m2 = group_sum<G>(s2) * inv_d;
+    const float m1 = xor_sum<G>(s1) * inv_d, m2 = xor_sum<G>(s2) * inv_d;
     if (!live) continue;
 #pragma unroll
     for (int k = 0; k < KV; ++k) {
@@ -298,33 +271,7 @@ __global__ __launch_bounds__(THREADS) void postnorm_bwd_kernel(NormArgs a) {
   }
 }
 
-// workgroup partials added in a fixed order (K15's finish: thread (channel, part) sums workgroups b = part mod 8, the eight parts
-// meet in LDS in part order)
-__global__ __launch_bounds__(256) void postnorm_finish_kernel(NormArgs a) {
-  __shared__ float red[8][33];
-  const int ch = threadIdx.x & 31, part = threadIdx.x >> 5, i = blockIdx.x * 32 + ch, n2 = 2 * a.D;
-  float s = 0.f;
-  if (i < n2)
-    for (int b = part; b < a.n_blocks; b += 8) s += a.partials[(size_t)b * n2 + i];
-  red[part][ch] = s;
-  __syncthreads();
-  if (part == 0 && i < n2) {
-    float t = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) t += red[q][ch];
-    float *dst = (i < a.D) ? a.g_gamma + i : a.g_beta + (i - a.D);
-    *dst = a.accumulate ? *dst + t : t;
-  }
-}
-
 static int norm_shape_ok(int64_t rows, int32_t D) { return rows >= 0 && D >= 2 && D <= 1024; }
-static int rows_per_block(int32_t D) { return D <= 32 ? 32 : D <= 64 ? 16 : D <= 128 ? 8 : 4; }
-static int norm_blocks(int64_t rows, int32_t D) {
-  const int rpb = rows_per_block(D);
-  int64_t b = (rows + rpb - 1) / rpb;
-  if (b > 1024) b = 1024;
-  return b < 1 ? 1 : (int)b;
-}
 
 #define P2C_PN_DISPATCH(KERNEL, grid)                                                                           \
   if (D <= 32) hipLaunchKernelGGL((KERNEL<8, 4>), grid, dim3(THREADS), 0, (hipStream_t)stream, a);              \
@@ -357,10 +304,9 @@ extern "C" int p2c_attn_drop_fwd(const float *qkv, float *out, float scale, int3
   if (S == 0) return 0;
   AttnArgs a{};
   a.qkv = qkv, a.out = out, a.S = S, a.N = N, a.heads = heads, a.hd = head_dim, a.scale = scale;
-  a.drop = make_drop(drop_p > 0.f ? drop_state : nullptr, drop_p, drop_site);
+  a.drop = DropRng(drop_p > 0.f ? drop_state : nullptr, drop_p, drop_site);
   hipLaunchKernelGGL(attn_fwd_kernel, dim3((unsigned)(S * heads)), dim3(THREADS), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_attn_drop_bwd(const float *qkv, const float *g_out, float *g_qkv, float scale, int32_t S, int32_t N,
@@ -370,17 +316,16 @@ extern "C" int p2c_attn_drop_bwd(const float *qkv, const float *g_out, float *g_
   if (S == 0) return 0;
   AttnArgs a{};
   a.qkv = qkv, a.g_out = g_out, a.g_qkv = g_qkv, a.S = S, a.N = N, a.heads = heads, a.hd = head_dim, a.scale = scale;
-  a.drop = make_drop(drop_p > 0.f ? drop_state : nullptr, drop_p, drop_site);
+  a.drop = DropRng(drop_p > 0.f ? drop_state : nullptr, drop_p, drop_site);
   hipLaunchKernelGGL(attn_bwd_kernel, dim3((unsigned)(S * heads)), dim3(THREADS), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_postnorm_supported(int32_t D) { return norm_shape_ok(0, D); }
 
 extern "C" int64_t p2c_postnorm_workspace_floats(int64_t rows, int32_t D) {
   if (!norm_shape_ok(rows, D)) return 0;
-  return (int64_t)norm_blocks(rows, D) * 2 * D;
+  return (int64_t)p2c_internal_norm_blocks(rows, D) * 2 * D;
 }
 
 static int norm_check(int64_t rows, int32_t D, void *drop_state, float drop_p) {
@@ -398,11 +343,10 @@ extern "C" int p2c_postnorm_fwd(const float *x, const float *s, const float *gam
   if (rows == 0) return 0;
   NormArgs a{};
   a.x = x, a.s = s, a.gamma = gamma, a.beta = beta, a.z = z, a.mean = mean, a.rstd = rstd, a.rows = rows, a.D = D, a.eps = eps;
-  a.drop = make_drop(drop_p > 0.f ? drop_state : nullptr, drop_p, drop_site);
-  const dim3 grid((unsigned)norm_blocks(rows, D));
+  a.drop = DropRng(drop_p > 0.f ? drop_state : nullptr, drop_p, drop_site);
+  const dim3 grid((unsigned)p2c_internal_norm_blocks(rows, D));
   P2C_PN_DISPATCH(postnorm_fwd_kernel, grid)
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_postnorm_bwd(const float *x, const float *s, const float *gamma, const float *mean, const float *rstd,
@@ -415,13 +359,11 @@ extern "C" int p2c_postnorm_bwd(const float *x, const float *s, const float *gam
   a.x = x, a.s = s, a.gamma = gamma, a.mean = const_cast<float *>(mean), a.rstd = const_cast<float *>(rstd), a.gz = g_z;
   a.gx = g_x, a.gs = g_s, a.g_gamma = g_gamma, a.g_beta = g_beta, a.partials = workspace, a.rows = rows, a.D = D;
   a.accumulate = accumulate;
-  a.drop = make_drop(drop_p > 0.f ? drop_state : nullptr, drop_p, drop_site);
-  a.n_blocks = rows > 0 ? norm_blocks(rows, D) : 0;
+  a.drop = DropRng(drop_p > 0.f ? drop_state : nullptr, drop_p, drop_site);
+  a.n_blocks = rows > 0 ? p2c_internal_norm_blocks(rows, D) : 0;
   if (rows > 0) {
     const dim3 grid((unsigned)a.n_blocks);
     P2C_PN_DISPATCH(postnorm_bwd_kernel, grid)
   }
-  hipLaunchKernelGGL(postnorm_finish_kernel, dim3((unsigned)((2 * D + 31) / 32)), dim3(256), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_internal_norm_finish(workspace, a.n_blocks, D, g_gamma, g_beta, accumulate, (hipStream_t)stream);   // K15's second launch
 }

@@ -9,29 +9,15 @@
 #include <math.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
+#include "p2c_lane_dev.h"
 
 namespace p2c_eval {
 
+using p2c_lane::xor_max;
+using p2c_lane::xor_min;
+using p2c_lane::xor_sum;
 constexpr int JP = P2C_JOINTS;   // prediction joints (CARLA skeleton)
-
-template <int G>
-__device__ __forceinline__ float gsum(float v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-template <int G>
-__device__ __forceinline__ float gmin(float v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
-  return v;
-}
-template <int G>
-__device__ __forceinline__ float gmax(float v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-  return v;
-}
 
 // ---- MPJPE + MRPE ------------------------------------------------------------------------------------------------------
 struct Pose3dArgs {
@@ -72,8 +58,8 @@ __global__ __launch_bounds__(256) void pose3d_kernel(const Pose3dArgs a) {
     }
   }
   // per clip: mean over joints and frames (mpjpe.py:40-41), mean over frames (mrpe.py:68-71); then sum over clips
-  float m = gsum<32>(dsum) / (float)(a.T * a.n_common);
-  float r = gsum<32>(rsum) / (float)a.T;
+  float m = xor_sum<32>(dsum) / (float)(a.T * a.n_common);
+  float r = xor_sum<32>(rsum) / (float)a.T;
   if (!clip_ok) m = 0.f, r = 0.f;
   const float m2 = m + __shfl_xor(m, 32, 64), r2 = r + __shfl_xor(r, 32, 64);
   if (lane == 0) a.partials[wave * 2] = m2, a.partials[wave * 2 + 1] = r2;
@@ -126,8 +112,8 @@ __global__ __launch_bounds__(256) void pck_kernel(const PckArgs a) {
   if (a.norm_mode == 0) {                                       // utils/tensors.py:12-26 over ALL gt joints
     const bool missing = !joint_ok || (gx < a.near_zero && gy < a.near_zero);
     const float inf = __builtin_inff();
-    const float x0 = gmin<G>(missing ? inf : gx), y0 = gmin<G>(missing ? inf : gy);
-    const float x1 = gmax<G>(missing ? -inf : gx), y1 = gmax<G>(missing ? -inf : gy);
+    const float x0 = xor_min<G>(missing ? inf : gx), y0 = xor_min<G>(missing ? inf : gy);
+    const float x1 = xor_max<G>(missing ? -inf : gx), y1 = xor_max<G>(missing ? -inf : gy);
     const float dx = x1 - x0, dy = y1 - y0;
     norm = sqrtf(dx * dx + dy * dy);
   } else {                                                      // hips_neck_extractor.py:6-13, extractor.py:27-28
@@ -153,7 +139,7 @@ __global__ __launch_bounds__(256) void pck_kernel(const PckArgs a) {
     const float dx = (p[0] - gx) / norm, dy = (p[1] - gy) / norm;
     correct = (sqrtf(dx * dx + dy * dy) < a.threshold) ? 1.f : 0.f;
   }
-  const float c = gsum<64>(correct), tot = gsum<64>(counted ? 1.f : 0.f);
+  const float c = xor_sum<64>(correct), tot = xor_sum<64>(counted ? 1.f : 0.f);
   if (lane == 0) a.partials[wave * 2] = c, a.partials[wave * 2 + 1] = tot;
 }
 
@@ -197,8 +183,7 @@ extern "C" int p2c_eval_pose3d(const float *pred, const float *gt, int32_t B, in
   hipLaunchKernelGGL(pose3d_kernel, dim3(blocks), dim3(256), 0, stream, a);
   hipLaunchKernelGGL(accumulate_kernel, dim3(1), dim3(256), 0, stream, (const float *)partials, blocks * 4, 2, state,
                      (double)B, world_pred ? (double)B : 0.0);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_eval_pck(const float *pred, const float *gt, const float *mask_src, int64_t N, int32_t Jp, int32_t Cp,
@@ -238,6 +223,5 @@ extern "C" int p2c_eval_pck(const float *pred, const float *gt, const float *mas
   else hipLaunchKernelGGL(pck_kernel<64>, dim3(blocks), dim3(256), 0, stream, a);
   // column 0 = correct -> state[0], column 1 = total -> state[2]; the "count" slots state[1], state[3] stay untouched
   hipLaunchKernelGGL(accumulate_kernel, dim3(1), dim3(256), 0, stream, (const float *)partials, blocks * 4, 2, state, 0.0, 0.0);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

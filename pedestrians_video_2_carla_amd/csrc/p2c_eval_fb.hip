@@ -11,6 +11,8 @@
 #include <math.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
+#include "p2c_lane_dev.h"
 #include "p2c_procrustes_dev.h"
 
 namespace p2c_fb {
@@ -25,12 +27,7 @@ struct Args {
   int32_t J, which;
 };
 
-template <int G>
-__device__ __forceinline__ double gsum(double v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
+using p2c_lane::xor_sum;
 
 __device__ __forceinline__ double norm3(double x, double y, double z) { return sqrt(x * x + y * y + z * z); }
 
@@ -51,15 +48,15 @@ __global__ __launch_bounds__(256) void fb_kernel(const Args a) {
 
   if (a.which & (M_MPJPE | M_WEIGHTED)) {
     const double d = norm3(p[0] - g[0], p[1] - g[1], p[2] - g[2]);
-    if (a.which & M_MPJPE) m[0] = gsum<G>(d);
-    if (a.which & M_WEIGHTED) m[1] = gsum<G>((a.w && joint_ok) ? (double)a.w[j] * d : d);
+    if (a.which & M_MPJPE) m[0] = xor_sum<G>(d);
+    if (a.which & M_WEIGHTED) m[1] = xor_sum<G>((a.w && joint_ok) ? (double)a.w[j] * d : d);
   }
   if (a.which & M_N) {                             // n_mpjpe: s = <g, p> / <p, p> over the frame (the two joint means cancel)
-    const double gp = gsum<G>(g[0] * p[0] + g[1] * p[1] + g[2] * p[2]);
-    const double pp = gsum<G>(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+    const double gp = xor_sum<G>(g[0] * p[0] + g[1] * p[1] + g[2] * p[2]);
+    const double pp = xor_sum<G>(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
     const double s = gp / pp;                      // 0/0 for an all-zero prediction: NaN, as in the tensor path
     const double d = norm3(s * p[0] - g[0], s * p[1] - g[1], s * p[2] - g[2]);
-    m[2] = gsum<G>(joint_ok ? d : 0.0);            // (a NaN scale must not leak in through the lanes past J of a finite frame)
+    m[2] = xor_sum<G>(joint_ok ? d : 0.0);            // (a NaN scale must not leak in through the lanes past J of a finite frame)
   }
   if (a.which & M_V) {                             // mean_velocity_error over the flattened (clip x frame) axis
     double d = 0.0;
@@ -68,17 +65,17 @@ __global__ __launch_bounds__(256) void fb_kernel(const Args a) {
       d = norm3(((double)pp[0] - p[0]) - ((double)gp[0] - g[0]), ((double)pp[1] - p[1]) - ((double)gp[1] - g[1]),
                 ((double)pp[2] - p[2]) - ((double)gp[2] - g[2]));
     }
-    m[3] = gsum<G>(d);
+    m[3] = xor_sum<G>(d);
   }
   if (a.which & M_PA) {                            // p_mpjpe, step for step
     double x0[3], y0[3];                           // centred, then scaled to unit Frobenius norm
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      const double mux = gsum<G>(g[k]) * invJ, muy = gsum<G>(p[k]) * invJ;
+      const double mux = xor_sum<G>(g[k]) * invJ, muy = xor_sum<G>(p[k]) * invJ;
       x0[k] = joint_ok ? g[k] - mux : 0.0, y0[k] = joint_ok ? p[k] - muy : 0.0;
     }
-    const double normX = sqrt(gsum<G>(x0[0] * x0[0] + x0[1] * x0[1] + x0[2] * x0[2]));
-    const double normY = sqrt(gsum<G>(y0[0] * y0[0] + y0[1] * y0[1] + y0[2] * y0[2]));
+    const double normX = sqrt(xor_sum<G>(x0[0] * x0[0] + x0[1] * x0[1] + x0[2] * x0[2]));
+    const double normY = sqrt(xor_sum<G>(y0[0] * y0[0] + y0[1] * y0[1] + y0[2] * y0[2]));
 #pragma unroll
     for (int k = 0; k < 3; ++k) {                  // coincident joints: 0/0 on the real lanes, NaN as in the tensor path
       x0[k] = joint_ok ? x0[k] / normX : 0.0, y0[k] = joint_ok ? y0[k] / normY : 0.0;
@@ -87,13 +84,13 @@ __global__ __launch_bounds__(256) void fb_kernel(const Args a) {
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
-      for (int c = 0; c < 3; ++c) H[r][c] = gsum<G>(x0[r] * y0[c]);
+      for (int c = 0; c < 3; ++c) H[r][c] = xor_sum<G>(x0[r] * y0[c]);
     p2c_procrustes::solve(H, R, ssum);
     // a (Y R) + t - X with a = ssum normX / normY and t = muX - a muY R  ==  normX (ssum (Y0 R) - X0), the offsets cancelled
     double e[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) e[c] = ssum * (y0[0] * R[0][c] + y0[1] * R[1][c] + y0[2] * R[2][c]) - x0[c];
-    m[4] = gsum<G>(joint_ok ? normX * norm3(e[0], e[1], e[2]) : 0.0);
+    m[4] = xor_sum<G>(joint_ok ? normX * norm3(e[0], e[1], e[2]) : 0.0);
   }
   // empty groups hold 0/0 here: selected away, not multiplied away. Every launched wavefront writes its row.
 #pragma unroll
@@ -157,6 +154,5 @@ extern "C" int p2c_eval_fb(const float *pred, const float *gt, const float *w, i
   const double scale_v = N > 1 ? (double)N / ((double)(N - 1) * (double)J) : 0.0;
   hipLaunchKernelGGL(fb_accumulate_kernel, dim3(1), dim3(256), 0, stream, (const float *)partials, waves, which, state, scale,
                      scale_v, (double)N);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 
 namespace p2c_fr {
 
@@ -375,6 +376,5 @@ extern "C" int p2c_clip_frames_fwd(const p2c_clip_frames_desc *d, void *stream) 
   hipError_t l = hipGetLastError();
   if (l != hipSuccess) return (int)l;
   hipLaunchKernelGGL(frames_out_kernel, dim3((unsigned)grid_b), dim3(256), 0, (hipStream_t)stream, b);
-  l = hipGetLastError();
-  return l == hipSuccess ? 0 : (int)l;
+  return p2c_host::launch_status();
 }

@@ -26,6 +26,7 @@
 #include <stdlib.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 #include "p2c_rec_dev.h"
 
 namespace p2c_gemm_impl {
@@ -953,8 +954,7 @@ extern "C" int p2c_gemm_tn(const float *a, int64_t lda, const float *b, int64_t 
   d.row_scale = row_scale, d.rows_per_scale = rows_per_scale;
   d.bias = bias_out, d.ws_bias = workspace + (int64_t)d.slices * M * N;
   hipStream_t s = (hipStream_t)stream_;
-  auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec = al(a) && al(b) && lda % 4 == 0 && ldb % 4 == 0 && M % 4 == 0 && N % 4 == 0;
+  const bool vec = p2c_host::aligned16(a, b) && lda % 4 == 0 && ldb % 4 == 0 && M % 4 == 0 && N % 4 == 0;
   const int bn = tn_bn(N);
   const dim3 grid(xcd_grid((int64_t)((M + BM - 1) / BM) * ((N + bn - 1) / bn) * d.slices));
   static const int no_fast = getenv("P2C_GEMM_NO_FAST") ? atoi(getenv("P2C_GEMM_NO_FAST")) : 0;      // (A/B timing)
@@ -971,7 +971,7 @@ extern "C" int p2c_gemm_tn(const float *a, int64_t lda, const float *b, int64_t 
 #undef P2C_TN
   const int64_t total = (int64_t)M * N;
   const int64_t n_all = total + (bias_out ? M : 0);
-  if (N % 4 == 0 && ldc % 4 == 0 && al(c) && al(workspace)) {
+  if (N % 4 == 0 && ldc % 4 == 0 && p2c_host::aligned16(c, workspace)) {
     const int64_t n_thr = total / 4 + (bias_out ? M : 0);
     if (d.slices <= 8)
       hipLaunchKernelGGL(tn_finish_vec_kernel, dim3((unsigned)((n_thr + 255) / 256 < 65536 ? (n_thr + 255) / 256 : 65536)), dim3(256), 0, s, d);
@@ -980,8 +980,7 @@ extern "C" int p2c_gemm_tn(const float *a, int64_t lda, const float *b, int64_t 
   } else {
     hipLaunchKernelGGL(tn_finish_kernel, dim3((unsigned)((n_all + 31) / 32 < 65536 ? (n_all + 31) / 32 : 65536)), dim3(256), 0, s, d);
   }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 #ifdef P2C_GEMM_TRACE
@@ -1008,8 +1007,7 @@ extern "C" int p2c_gemm(const p2c_gemm_desc *desc, void *stream_) {
   if ((int64_t)((d.M + BM - 1) / BM) * ((d.N + 31) / 32) > 0x7fffffffll) return P2C_E_SHAPE;
   hipStream_t s = (hipStream_t)stream_;
   // 16-byte loads need 16-byte aligned rows: every leading dimension a multiple of 4 floats, bases aligned, K (NT) / N (NN) too
-  auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec = al(d.a) && al(d.b) && d.lda % 4 == 0 && d.ldb % 4 == 0 && d.K % 4 == 0 && (d.trans_b || d.N % 4 == 0);
+  const bool vec = p2c_host::aligned16(d.a, d.b) && d.lda % 4 == 0 && d.ldb % 4 == 0 && d.K % 4 == 0 && (d.trans_b || d.N % 4 == 0);
   // Column tile: 64 (four waves of 32 x 64 side by side) -- measured ahead of the 2 x 2 arrangement of 64 x 64 waves at every
   // wide shape of cfg5 (NT 832-wide outputs +6..10 %, equal at 2 496; 120 VGPRs -> four workgroups per CU), 32 for the NN form
   // (another 3..5 %) and for N <= 32. Small problems (the 8 192-row projections around the Seq2Seq recurrences) take the
@@ -1034,6 +1032,5 @@ extern "C" int p2c_gemm(const p2c_gemm_desc *desc, void *stream_) {
     else if (bn == 64) launch<64, false>(d, vec, s);
     else launch<32, false>(d, vec, s);
   }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

@@ -27,6 +27,8 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_lane_dev.h"
+#include "p2c_host.h"
 #include "p2c_adam_math.h"
 
 namespace p2c_grad_clip {
@@ -49,8 +51,7 @@ static int64_t sqnorm_blocks(int64_t n) {
 // lanes -> wave (xor butterfly: every lane ends with the same sum) -> workgroup (the four wave sums added in wave order by
 // every thread that asks): one fixed order, the same in every workgroup
 __device__ __forceinline__ double block_sum(double v, double *sw) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  v = p2c_lane::xor_sum<64>(v);
   if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = v;
   __syncthreads();
   double s = sw[0];
@@ -207,6 +208,5 @@ extern "C" int p2c_adamw_step_clipped(const p2c_adamw_desc *desc, const p2c_clip
   if (blocks > 2048) blocks = 2048;
   if (norm) launch_step<P2C_CLIP_NORM>(*desc, a, (unsigned)blocks, stream);
   else launch_step<P2C_CLIP_VALUE>(*desc, a, (unsigned)blocks, stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

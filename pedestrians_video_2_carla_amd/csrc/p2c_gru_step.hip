@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 #include "p2c_rec_step_dev.h"
 
 namespace p2c_gru_step {
@@ -167,8 +168,7 @@ extern "C" int p2c_gru_steps_fwd(const p2c_gru_desc *d, void *stream) {
   if (!a.gx || !a.out) return P2C_E_NULL;                        // out carries the state from one launch to the next
   if (a.B == 0) return 0;
   for (int t = 0; t < a.T; ++t) hipLaunchKernelGGL(gru_step_fwd_kernel, steps_grid(a.B, a.H), dim3(NT), 0, (hipStream_t)stream, a, t);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_gru_steps_bwd(const p2c_gru_desc *d, float *workspace, void *stream) {
@@ -182,6 +182,5 @@ extern "C" int p2c_gru_steps_bwd(const p2c_gru_desc *d, float *workspace, void *
   if (a.B == 0 || a.T == 0) return 0;
   for (int t = a.T - 1; t >= 0; --t) hipLaunchKernelGGL(gru_step_bwd_kernel, steps_grid(a.B, a.H), dim3(NT), 0, (hipStream_t)stream, a, t);
   if (a.g_h0) hipLaunchKernelGGL(gru_step_bwd_kernel, steps_grid(a.B, a.H), dim3(NT), 0, (hipStream_t)stream, a, -1);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

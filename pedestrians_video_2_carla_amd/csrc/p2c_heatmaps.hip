@@ -30,6 +30,8 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_lane_dev.h"
+#include "p2c_host.h"
 
 namespace p2c_hm {
 
@@ -117,16 +119,6 @@ struct LossArgs {
   int32_t pred_channels[kMaxMaps], gt_channels[kMaxMaps];
 };
 
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(64) void heatmaps_loss_maps_kernel(const LossArgs a) {
   const int64_t pair = blockIdx.x;                                 // (b, t, k), k fastest
@@ -141,7 +133,7 @@ __global__ __launch_bounds__(64) void heatmaps_loss_maps_kernel(const LossArgs a
     acc = fmaf(d, d, acc);
     zeros |= !(t != 0.f);                                          // a NaN target cell is != 0, as in the reference
   }
-  acc = wave_sum_f(acc);
+  acc = p2c_lane::xor_sum<64>(acc);
   const int any_zero = __any(zeros);
   if (threadIdx.x == 0) {
     a.partials[pair] = acc;
@@ -160,7 +152,7 @@ __global__ __launch_bounds__(256) void heatmaps_loss_finish_kernel(const LossArg
       const int64_t b = e / a.K, pair = (b * a.T + t) * a.K + (e - b * a.K);
       if (a.flags[pair]) s += (double)a.partials[pair], n += 1.0;
     }
-    s = wave_sum_d(s), n = wave_sum_d(n);
+    s = p2c_lane::xor_sum<64>(s), n = p2c_lane::xor_sum<64>(n);
     const bool use = n > 0.0 && !(s != s);
     const double div = n * (double)a.cells;
     if (use) total += s / div;
@@ -290,8 +282,7 @@ static int check_loss(const p2c_heatmaps_loss_desc *d, bool bwd, LossArgs &a) {
 using namespace p2c_hm;
 
 static int launched() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_heatmap_targets_fwd(const p2c_heatmap_targets_desc *d, void *stream) {

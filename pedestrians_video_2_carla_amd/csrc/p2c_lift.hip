@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 
 #include "p2c_mlp_dev.h"
 #include "p2c_pose_head_dev.h"
@@ -236,6 +237,5 @@ extern "C" int p2c_lift_fwd(const p2c_lift_desc *d, void *stream) {
   const int cap = d->max_blocks > 0 && d->max_blocks < kMaxBlocks ? d->max_blocks : kMaxBlocks;
   const int grid = d->B < cap ? d->B : cap;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTH), (size_t)LDS_FLOATS * sizeof(float), (hipStream_t)stream, a);
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
+  return p2c_host::launch_status();
 }

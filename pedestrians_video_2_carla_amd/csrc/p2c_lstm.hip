@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 #include "p2c_rec_dev.h"
 
 namespace p2c_lstm {
@@ -517,8 +518,7 @@ static int check(const p2c_lstm_desc *d, Args &a) {
   if (d->drop_state) {
     if (!(d->drop_p >= 0.f && d->drop_p < 1.f)) return P2C_E_SHAPE;
     a.out_drop = d->out_drop;
-    a.rng.state = d->drop_state, a.rng.site = d->drop_site, a.rng.scale = 1.f / (1.f - d->drop_p);
-    a.rng.thresh = (uint32_t)((double)d->drop_p * 4294967296.0);
+    a.rng = DropRng(d->drop_state, d->drop_p, d->drop_site);
   }
   return 0;
 }
@@ -574,8 +574,7 @@ extern "C" int p2c_lstm_rec_fwd(const p2c_lstm_desc *d, void *stream) {
     const dim3 grid((unsigned)((a.B + TS - 1) / TS));
     P2C_LSTM_DISPATCH(lstm_rec_fwd_kernel, false)
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_lstm_rec_bwd(const p2c_lstm_desc *d, void *stream) {
@@ -591,6 +590,5 @@ extern "C" int p2c_lstm_rec_bwd(const p2c_lstm_desc *d, void *stream) {
     const dim3 grid((unsigned)((a.B + TS - 1) / TS));
     P2C_LSTM_DISPATCH(lstm_rec_bwd_kernel, true)
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 #include "p2c_rec_step_dev.h"
 
 namespace p2c_lstm_step {
@@ -184,8 +185,7 @@ extern "C" int p2c_lstm_steps_fwd(const p2c_lstm_desc *d, void *stream) {
   if (!a.gx || !a.out || !a.acts || !a.cs) return P2C_E_NULL;   // cs carries the cell state from one launch to the next
   if (a.B == 0) return 0;
   for (int t = 0; t < a.T; ++t) hipLaunchKernelGGL(lstm_step_fwd_kernel, steps_grid(a.B, a.H), dim3(NT), 0, (hipStream_t)stream, a, t);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_lstm_steps_bwd(const p2c_lstm_desc *d, float *workspace, void *stream) {
@@ -198,6 +198,5 @@ extern "C" int p2c_lstm_steps_bwd(const p2c_lstm_desc *d, float *workspace, void
   if (a.B == 0 || a.T == 0) return 0;
   for (int t = a.T - 1; t >= 0; --t) hipLaunchKernelGGL(lstm_step_bwd_kernel, steps_grid(a.B, a.H), dim3(NT), 0, (hipStream_t)stream, a, t);
   if (a.g_h0) hipLaunchKernelGGL(lstm_step_bwd_kernel, steps_grid(a.B, a.H), dim3(NT), 0, (hipStream_t)stream, a, -1);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 #include "p2c_adam_math.h"
 
 #include "p2c_mlp_dev.h"
@@ -586,7 +587,7 @@ __global__ __launch_bounds__(256) void mlp_reduce_small_kernel(const MlpArgs a, 
 
 using namespace p2c_mlp;
 
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using p2c_host::aligned16;
 
 static int fill(MlpArgs &a, const p2c_mlp_desc *d) {
   if (!d || !d->x) return P2C_E_NULL;
@@ -799,8 +800,7 @@ extern "C" int p2c_mlp_pack(const p2c_mlp_desc *d, void *stream_) {
   if (rc) return rc;
   if (!a.w_image) return P2C_E_NULL;
   hipLaunchKernelGGL(mlp_pack_kernel, dim3((a.w_total + 255) / 256), dim3(256), 0, (hipStream_t)stream_, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int64_t p2c_mlp_image_index(const p2c_mlp_desc *d, int32_t *index, int64_t capacity) {
@@ -870,8 +870,7 @@ extern "C" int p2c_mlp_fwd(const p2c_mlp_desc *d, void *stream_) {
   } else {
     hipLaunchKernelGGL(pick(a, prec, false), dim3(n_blocks(a.N)), dim3(64 * WAVES), lds, (hipStream_t)stream_, a);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_mlp_bwd(const p2c_mlp_desc *d, void *stream_) {
@@ -928,6 +927,5 @@ extern "C" int p2c_mlp_bwd(const p2c_mlp_desc *d, void *stream_) {
     else
       hipLaunchKernelGGL(mlp_reduce_kernel<false>, rgrid, rblock, 0, (hipStream_t)stream_, a, blocks, p2c_adamw_desc{}, nullptr);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

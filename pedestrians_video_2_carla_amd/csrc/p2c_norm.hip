@@ -17,6 +17,8 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
+#include "p2c_lane_dev.h"
 
 namespace p2c_norm {
 
@@ -30,13 +32,6 @@ struct Args {
   int32_t D, accumulate, n_blocks;
   float eps;
 };
-
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {         // butterfly over the G lanes of a row
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // G lanes per row, KV float4 per lane: channel of (k, l) = (k G + l) * 4
 template <int G, int KV>
@@ -65,7 +60,7 @@ __global__ __launch_bounds__(THREADS) void ln_fwd_kernel(const Args a) {
       v[k] = (live && on[k]) ? *reinterpret_cast<const f32x4 *>(a.x + r * D + (k * G + l) * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
       s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
     }
-    const float mean = group_sum<G>(s) * inv_d;
+    const float mean = p2c_lane::xor_sum<G>(s) * inv_d;
     float q = 0.f;
 #pragma unroll
     for (int k = 0; k < KV; ++k)
@@ -76,7 +71,7 @@ __global__ __launch_bounds__(THREADS) void ln_fwd_kernel(const Args a) {
           q = fmaf(dlt, dlt, q);
         }
       }
-    const float rstd = rsqrtf(group_sum<G>(q) * inv_d + a.eps);
+    const float rstd = rsqrtf(p2c_lane::xor_sum<G>(q) * inv_d + a.eps);
     if (!live) continue;
 #pragma unroll
     for (int k = 0; k < KV; ++k)
@@ -128,7 +123,7 @@ __global__ __launch_bounds__(THREADS) void ln_bwd_kernel(const Args a) {
         db[k][c] += gv[c];
       }
     }
-    const float m1 = group_sum<G>(s1) * inv_d, m2 = group_sum<G>(s2) * inv_d;
+    const float m1 = p2c_lane::xor_sum<G>(s1) * inv_d, m2 = p2c_lane::xor_sum<G>(s2) * inv_d;
     if (!live) continue;
 #pragma unroll
     for (int k = 0; k < KV; ++k)
@@ -205,11 +200,23 @@ static int rows_per_block(int32_t D) { return D <= 32 ? 32 : D <= 64 ? 16 : D <=
 
 }  // namespace p2c_norm
 
+// ---- shared with K20b (p2c_encoder.hip), whose row kernels leave the same partial rows ---------------------------------------
+int p2c_internal_norm_blocks(int64_t rows, int32_t D) { return p2c_norm::blocks_for(rows, p2c_norm::rows_per_block(D)); }
+
+int p2c_internal_norm_finish(const float *partials, int32_t n_blocks, int32_t D, float *g_gamma, float *g_beta, int32_t accumulate,
+                             hipStream_t stream) {
+  p2c_norm::Args a{};
+  a.partials = const_cast<float *>(partials), a.n_blocks = n_blocks, a.D = D, a.g_gamma = g_gamma, a.g_beta = g_beta;
+  a.accumulate = accumulate;
+  hipLaunchKernelGGL(p2c_norm::ln_bwd_finish_kernel, dim3((unsigned)((2 * D + 31) / 32)), dim3(256), 0, stream, a);
+  return p2c_host::launch_status();
+}
+
 extern "C" int p2c_layernorm_supported(int32_t D) { return p2c_norm::shape_ok(0, D); }
 
 extern "C" int64_t p2c_layernorm_workspace_floats(int64_t rows, int32_t D) {
   if (!p2c_norm::shape_ok(rows, D)) return 0;
-  return (int64_t)p2c_norm::blocks_for(rows, p2c_norm::rows_per_block(D)) * 2 * D;
+  return (int64_t)p2c_internal_norm_blocks(rows, D) * 2 * D;
 }
 
 extern "C" int p2c_layernorm_fwd(const float *x, const float *gamma, const float *beta, float *y, float *mean, float *rstd,
@@ -217,14 +224,13 @@ extern "C" int p2c_layernorm_fwd(const float *x, const float *gamma, const float
   using namespace p2c_norm;
   if (!x || !gamma || !beta || !y || !mean || !rstd) return P2C_E_NULL;
   if (!shape_ok(rows, D)) return P2C_E_SHAPE;
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) != 0) return P2C_E_SHAPE;
+  if (!p2c_host::aligned16(x, y)) return P2C_E_SHAPE;
   if (rows == 0) return 0;
   Args a{};
   a.x = x, a.gamma = gamma, a.beta = beta, a.y = y, a.mean = mean, a.rstd = rstd, a.rows = rows, a.D = D, a.eps = eps;
-  const dim3 grid((unsigned)blocks_for(rows, rows_per_block(D)));
+  const dim3 grid((unsigned)p2c_internal_norm_blocks(rows, D));
   P2C_LN_DISPATCH(ln_fwd_kernel, grid)
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_layernorm_bwd(const float *x, const float *gamma, const float *mean, const float *rstd, const float *gy,
@@ -233,19 +239,14 @@ extern "C" int p2c_layernorm_bwd(const float *x, const float *gamma, const float
   using namespace p2c_norm;
   if (!x || !gamma || !mean || !rstd || !gy || !gx || !g_gamma || !g_beta || !partials) return P2C_E_NULL;
   if (!shape_ok(rows, D)) return P2C_E_SHAPE;
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(gx)) & 15) != 0) return P2C_E_SHAPE;
+  if (!p2c_host::aligned16(x, gy, gx, gx_add)) return P2C_E_SHAPE;
   Args a{};
   a.x = x, a.gamma = gamma, a.mean = const_cast<float *>(mean), a.rstd = const_cast<float *>(rstd), a.gy = gy, a.gx = gx, a.g_gamma = g_gamma, a.g_beta = g_beta;
   a.partials = partials, a.rows = rows, a.D = D, a.accumulate = accumulate, a.gx_add = gx_add;
-  if (gx_add && (reinterpret_cast<uintptr_t>(gx_add) & 15) != 0) return P2C_E_SHAPE;
-  a.n_blocks = blocks_for(rows, rows_per_block(D));
+  a.n_blocks = rows > 0 ? p2c_internal_norm_blocks(rows, D) : 0;
   if (rows > 0) {
     const dim3 grid((unsigned)a.n_blocks);
     P2C_LN_DISPATCH(ln_bwd_kernel, grid)
-  } else {
-    a.n_blocks = 0;
   }
-  hipLaunchKernelGGL(ln_bwd_finish_kernel, dim3((unsigned)((2 * D + 31) / 32)), dim3(256), 0, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_internal_norm_finish(partials, a.n_blocks, D, g_gamma, g_beta, accumulate, (hipStream_t)stream);
 }

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 #include "p2c_adam_math.h"
 
 namespace p2c_optim {
@@ -85,6 +86,5 @@ extern "C" int p2c_adamw_step(const p2c_adamw_desc *desc, void *stream_) {
     hipLaunchKernelGGL(p2c_optim::adamw_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, *desc);
   else
     hipLaunchKernelGGL(p2c_optim::adamw_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, *desc);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

@@ -30,6 +30,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "p2c_lane_dev.h"
+#include "p2c_host.h"
 #include "p2c_pose_head_dev.h"
 
 namespace p2c_pcl {
@@ -135,8 +137,7 @@ __global__ __launch_bounds__(64) void pose_change_loss_fwd_kernel(const Args a) 
   for (int i = lane; i < (int)gridDim.x; i += 64)
     s += (double)__uint_as_float(__hip_atomic_load(reinterpret_cast<unsigned *>(a.partials) + i, __ATOMIC_RELAXED,
                                                    __HIP_MEMORY_SCOPE_AGENT));
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+  s = p2c_lane::xor_sum<64>(s);
   if (lane == 0) *a.loss = (float)(s * a.inv_n);
 }
 
@@ -260,8 +261,7 @@ extern "C" int p2c_pose_change_loss_fwd(const p2c_pose_change_loss_desc *d, void
   if (e != hipSuccess) return (int)e;
   if (d->pred_is_6d) hipLaunchKernelGGL(pose_change_loss_fwd_kernel<true>, dim3(blocks), dim3(64), 0, stream, a);
   else hipLaunchKernelGGL(pose_change_loss_fwd_kernel<false>, dim3(blocks), dim3(64), 0, stream, a);
-  e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_pose_change_loss_bwd(const p2c_pose_change_loss_desc *d, void *stream_) {
@@ -273,6 +273,5 @@ extern "C" int p2c_pose_change_loss_bwd(const p2c_pose_change_loss_desc *d, void
   hipStream_t stream = (hipStream_t)stream_;
   if (d->pred_is_6d) hipLaunchKernelGGL(pose_change_loss_bwd_kernel<true>, dim3(blocks), dim3(64), 0, stream, a);
   else hipLaunchKernelGGL(pose_change_loss_bwd_kernel<false>, dim3(blocks), dim3(64), 0, stream, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

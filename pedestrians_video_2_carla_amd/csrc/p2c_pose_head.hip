@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 
 #include "p2c_pose_head_dev.h"
 
@@ -841,8 +842,7 @@ static int pose_head_fwd_impl(const p2c_pose_head_desc *desc, void *stream_, int
   const bool sixd = d.kind == P2C_KIND_POSE_CHANGES_6D || d.kind == P2C_KIND_RELATIVE_ROT_6D;
   if (d.defer_loss_finalize == 2 && tp && !pkd && sixd) {     // "train": the backward call does all of it
     hipLaunchKernelGGL(pose_head_count_tp, dim3((unsigned)d.B), dim3(tp_threads(d.T)), 0, stream, d);
-    hipError_t e0 = hipGetLastError();
-    return e0 == hipSuccess ? 0 : (int)e0;
+    return p2c_host::launch_status();
   }
   const dim3 tp_grid((unsigned)d.B), tp_block(tp_threads(d.T)), pk_grid(grid_pk(d.B));
   if (!mat && use_chain(d)) {            // large batch of the training configuration: eight clips per wavefront
@@ -851,8 +851,7 @@ static int pose_head_fwd_impl(const p2c_pose_head_desc *desc, void *stream_, int
     if (!(which & 2)) return 0;
     hipLaunchKernelGGL(loss_finalize, dim3(1), dim3(256), 0, stream, (const float *)d.partials, (int)p2c_internal_chain_waves(d.B),
                        n3_elems_host(d), d.gt2d ? 1 : 0, d.gt3d ? 1 : 0, d.loss_sums, d.losses, 0.f);
-    hipError_t ec = hipGetLastError();
-    return ec == hipSuccess ? 0 : (int)ec;
+    return p2c_host::launch_status();
   }
 #define P2C_LAUNCH_ROT_FWD(KIND)                                                                                \
   if (mat) hipLaunchKernelGGL((pose_head_rot_fwd<KIND, true>), grid, block, 0, stream, d);                      \
@@ -887,8 +886,7 @@ static int pose_head_fwd_impl(const p2c_pose_head_desc *desc, void *stream_, int
   float n3 = (float)((double)d.B * (double)(d.t1 - d.t0) * (double)d.n_common3d * 3.0);
   hipLaunchKernelGGL(loss_finalize, dim3(1), dim3(256), 0, stream, (const float *)d.partials, n_waves, n3,
                      d.gt2d ? 1 : 0, d.gt3d ? 1 : 0, d.loss_sums, d.losses, nrot_elems_host(d));
-  e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_pose_head_fwd(const p2c_pose_head_desc *desc, void *stream_) { return pose_head_fwd_impl(desc, stream_, 3); }

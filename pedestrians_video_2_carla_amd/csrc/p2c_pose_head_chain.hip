@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 
 #include "p2c_pose_head_dev.h"
 
@@ -489,14 +490,12 @@ int p2c_internal_chain_fwd(const p2c_pose_head_desc &d, hipStream_t stream) {
     hipLaunchKernelGGL(chain::pose_head_chain_fwd<P2C_KIND_POSE_CHANGES_6D>, chain_grid(d.B), dim3(256), kChainLds, stream, d);
   else
     hipLaunchKernelGGL(chain::pose_head_chain_fwd<P2C_KIND_RELATIVE_ROT_6D>, chain_grid(d.B), dim3(256), kChainLds, stream, d);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 int p2c_internal_chain_bwd(const p2c_pose_head_desc &d, const GradLosses &gl, float *grad_y, hipStream_t stream) {
   if (d.kind == P2C_KIND_POSE_CHANGES_6D)
     hipLaunchKernelGGL(chain::pose_head_chain_bwd<P2C_KIND_POSE_CHANGES_6D>, chain_grid(d.B), dim3(256), kChainLdsBwd, stream, d, gl, grad_y);
   else
     hipLaunchKernelGGL(chain::pose_head_chain_bwd<P2C_KIND_RELATIVE_ROT_6D>, chain_grid(d.B), dim3(256), kChainLdsBwd, stream, d, gl, grad_y);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

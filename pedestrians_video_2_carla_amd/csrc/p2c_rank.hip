@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 
 namespace p2c_rank {
 
@@ -420,8 +421,7 @@ extern "C" int p2c_rank_curves(const p2c_rank_desc *d, void *workspace, void *st
     }
     hipLaunchKernelGGL(rank_lds_kernel, dim3(C), dim3(NT_LDS), lds, st, d->scores, d->targets, N, C, M, d->thresholds, d->tps, d->fps,
                        d->n_points, d->n_pos, d->auroc, d->n_valid);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return p2c_host::launch_status();
   }
   if (!workspace) return P2C_E_NULL;
   const int tiles = (int)tiles_of(N);
@@ -454,8 +454,7 @@ extern "C" int p2c_rank_curves(const p2c_rank_desc *d, void *workspace, void *st
                      d->fps);
   hipLaunchKernelGGL(finish_kernel, dim3(C), dim3(NT_LDS), 0, st, (const int32_t *)d->tps, (const int32_t *)d->fps, N,
                      (const int *)totals, d->n_points, d->n_pos, d->auroc, d->n_valid);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_rank_scores(const float *logits, const int64_t *targets, int64_t B, int32_t C, int32_t flags, float *out_scores,
@@ -471,6 +470,5 @@ extern "C" int p2c_rank_scores(const float *logits, const int64_t *targets, int6
   if (grid > 1024) grid = 1024;
   hipLaunchKernelGGL(rank_scores_kernel, dim3((unsigned)grid), dim3(NT), 0, (hipStream_t)stream, logits, targets, B, (int)C,
                      binary ? 1 : 0, out_scores, out_targets, row_offset);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

@@ -66,6 +66,18 @@ struct DropRng {
   int32_t site;          // distinguishes the dropout sites that share a state
   uint32_t k0, k1;       // per-launch keys (drop_begin: the raw seed words; drop_keys: the keys)
   uint32_t thresh_step;  // the step the launch draws for (drop_begin)
+
+  DropRng() = default;
+  // the host's set-up of a site: p >= 1 drops everything without dividing by zero. The caller decides when
+  // `state` is NULL (no dropout drawn here).
+  __host__ __device__ DropRng(void *state_, float p, int32_t site_)
+      : state(static_cast<int32_t *>(state_)),
+        thresh(p >= 1.f ? 0xFFFFFFFFu : (uint32_t)((double)p * 4294967296.0)),
+        scale(p >= 1.f ? 0.f : 1.f / (1.f - p)),
+        site(site_),
+        k0(0),
+        k1(0),
+        thresh_step(0) {}
 };
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {      // "lowbias32" integer finaliser: full avalanche
   x ^= x >> 16, x *= 0x7feb352du;
@@ -82,23 +94,22 @@ __device__ __forceinline__ void drop_begin(DropRng &r, const bool backward) {
   r.k0 = (uint32_t)r.state[0], r.k1 = (uint32_t)r.state[1];
   r.thresh_step = backward ? (uint32_t)r.state[3] - 1u : (uint32_t)r.state[2];
 }
-__device__ __forceinline__ void drop_keys(DropRng &r, const bool backward) {
+// The launch's keys without the state write: for a launch whose state word is left by one thread elsewhere (p2c_gemm.hip, where
+// workgroup 0 is not always a tile's).
+__device__ __forceinline__ void drop_keys_only(DropRng &r) {
   if (!r.state) return;
   const uint32_t s0 = r.k0, s1 = r.k1, step = r.thresh_step;
   r.k0 = mix32(s0 ^ (step * 0x9E3779B9u) ^ ((uint32_t)(r.site + 1) * 0x632BE59Bu));   // (the site in BOTH keys: with k1 alone two sites' hashes
                                                                                        // differ by a constant xor -- their masks are dependent)
   r.k1 = mix32(s1 + step + 0x85EBCA6Bu * (uint32_t)(r.site + 1));
+}
+__device__ __forceinline__ void drop_keys(DropRng &r, const bool backward) {
+  if (!r.state) return;
+  const uint32_t step = r.thresh_step;
+  drop_keys_only(r);
   // forward: next = step + 1 (the backward reads it); backward: step = next (the next forward reads it). No launch reads the word
   // it writes, so the moment of the store does not matter.
   if (blockIdx.x == 0 && threadIdx.x == 0) r.state[backward ? 2 : 3] = (int32_t)(step + 1u);
-}
-// The keys of drop_keys without the state write: for a launch whose state word is left by one thread elsewhere (p2c_gemm.hip, where
-// workgroup 0 is not always a tile's).
-__device__ __forceinline__ void drop_keys_only(DropRng &r) {
-  if (!r.state) return;
-  const uint32_t s0 = r.k0, s1 = r.k1, step = r.thresh_step;
-  r.k0 = mix32(s0 ^ (step * 0x9E3779B9u) ^ ((uint32_t)(r.site + 1) * 0x632BE59Bu));
-  r.k1 = mix32(s1 + step + 0x85EBCA6Bu * (uint32_t)(r.site + 1));
 }
 __device__ __forceinline__ float drop_value(const DropRng &r, const uint32_t e) {
   // one Fibonacci multiply spreads the element index, the launch key shifts it, one avalanche finaliser: three 32-bit multiplies

@@ -37,6 +37,7 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 #include "p2c_mlp_dev.h"
 
 namespace p2c_relu_stack {
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(RL * RG) void relu_stack_reduce_kernel(const StackA
   }
 }
 
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using p2c_host::aligned16;
 
 // geometry only (no pointer is looked at): 0, or P2C_E_SHAPE for widths the kernel does not cover
 static int fill_shape(StackArgs &a, const p2c_relu_stack_desc *d) {
@@ -324,8 +325,7 @@ extern "C" int p2c_relu_stack_fwd(const p2c_relu_stack_desc *d, void *stream_) {
   if (a.N == 0) return 0;
   allow_big_lds();
   hipLaunchKernelGGL(relu_stack_fwd_kernel, dim3(n_blocks(a.N)), dim3(64 * WAVES), lds_fwd(a), (hipStream_t)stream_, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_relu_stack_bwd(const p2c_relu_stack_desc *d, void *stream_) {
@@ -339,6 +339,5 @@ extern "C" int p2c_relu_stack_bwd(const p2c_relu_stack_desc *d, void *stream_) {
   const int blocks = n_blocks(a.N);           // N == 0: one workgroup writes a zero partial, the gradients are zero
   hipLaunchKernelGGL(relu_stack_bwd_kernel, dim3(blocks), dim3(64 * WAVES), lds_bwd(a), (hipStream_t)stream_, a);
   hipLaunchKernelGGL(relu_stack_reduce_kernel, dim3(a.n_tiles_w * (64 / RL)), dim3(RL * RG), 0, (hipStream_t)stream_, a, blocks);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

@@ -24,6 +24,7 @@
 #include <string.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 #include "p2c_rec_dev.h"
 
 namespace p2c_s2s {
@@ -702,8 +703,7 @@ static int fill(Args &a, const p2c_decoder_desc *d) {
   a.force = d->force, a.target = d->target;
   if (d->drop_state) {
     if (!(d->drop_p >= 0.f && d->drop_p < 1.f)) return P2C_E_SHAPE;
-    a.rng.state = d->drop_state, a.rng.site = d->drop_site, a.rng.scale = 1.f / (1.f - d->drop_p);
-    a.rng.thresh = (uint32_t)((double)d->drop_p * 4294967296.0);
+    a.rng = DropRng(d->drop_state, d->drop_p, d->drop_site);
   }
   return 0;
 }
@@ -761,8 +761,7 @@ extern "C" int p2c_decoder_fwd(const p2c_decoder_desc *d, void *stream) {
     else if (a.O <= 80) hipLaunchKernelGGL((decoder_fwd_wide_kernel<20, 2>), grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
     else hipLaunchKernelGGL((decoder_fwd_wide_kernel<40, 3>), grid, dim3(256), image_bytes(), (hipStream_t)stream, a);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_decoder_bwd(const p2c_decoder_desc *d, void *stream) {
@@ -791,6 +790,5 @@ extern "C" int p2c_decoder_bwd(const p2c_decoder_desc *d, void *stream) {
       hipLaunchKernelGGL(decoder_ghid_kernel, dim3(nh), dim3(256), 0, (hipStream_t)stream, a.g_k1, a.w_hh1, a.g_hid1, a.B);
     }
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 #include "p2c_adam_math.h"
 #include "p2c_mlp_dev.h"
 #include "p2c_pose_head_dev.h"
@@ -1115,8 +1116,7 @@ extern "C" int p2c_count_target_pairs(const p2c_pose_head_desc *desc, float *cou
   int rc = p2c_internal_validate_pose_head(&d);
   if (rc) return rc;
   hipLaunchKernelGGL(count_pairs_kernel, dim3((unsigned)d.B), dim3(256), 0, (hipStream_t)stream_, d, counts);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }
 
 extern "C" int p2c_train_step(const p2c_train_step_desc *desc, const float *const grad_losses_[3], void *stream_) {
@@ -1226,12 +1226,10 @@ extern "C" int p2c_train_step_launch(const p2c_train_step_desc *desc, const floa
     const dim3 grid_r((unsigned)(tiles * (64 / RED_L) + 1));
     if (adam) hipLaunchKernelGGL(wgrad_reduce_kernel<true>, grid_r, dim3(RED_L * RED_G), 0, stream, wa, blocks, o);
     else hipLaunchKernelGGL(wgrad_reduce_kernel<false>, grid_r, dim3(RED_L * RED_G), 0, stream, wa, blocks, o);
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return p2c_host::launch_status();
   }
   const dim3 grid_b((unsigned)(tiles * KS + 1));
   if (adam) hipLaunchKernelGGL(train_wgrad_kernel<true>, grid_b, dim3(64 * WG_WAVES), 0, stream, wa, o);
   else hipLaunchKernelGGL(train_wgrad_kernel<false>, grid_b, dim3(64 * WG_WAVES), 0, stream, wa, o);
-  e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "../../include/p2c.h"
+#include "p2c_host.h"
 #include "p2c_mlp_dev.h"
 #include "p2c_pose_head_dev.h"
 #include "p2c_pose_head_chain_dev.h"
@@ -989,6 +990,5 @@ int p2c_internal_train_stream_launch(const p2c_pose_head_desc &d, const p2c::Gra
     hipLaunchKernelGGL(train_stream_kernel<P2C_KIND_POSE_CHANGES_6D>, grid, dim3(64 * SW), lds_bytes, stream, d, gl, m);
   else
     hipLaunchKernelGGL(train_stream_kernel<P2C_KIND_RELATIVE_ROT_6D>, grid, dim3(64 * SW), lds_bytes, stream, d, gl, m);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return p2c_host::launch_status();
 }

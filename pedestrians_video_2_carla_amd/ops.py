@@ -8,7 +8,7 @@ import os
 import warnings
 import weakref
 from dataclasses import dataclass, field
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -1603,6 +1603,24 @@ def _sink(p: Tensor) -> Optional[Tensor]:
     return g if (g is not None and g.is_cuda and g.dtype == torch.float32 and g.stride(-1) == 1) else None
 
 
+def _group_sinks(*params: Optional[Tensor]) -> List[Optional[Tensor]]:
+    """The sinks of parameters whose gradients leave through one launch, i.e. under one accumulate flag (``None``: a parameter
+    the layer does not have). Either every parameter of the group has a sink or none is used: all ``None`` then."""
+    sinks = [None if p is None else _sink(p) for p in params]
+    if any(s is None for p, s in zip(params, sinks) if p is not None):
+        sinks = [None] * len(params)
+    return sinks
+
+
+def _grad_target(sink: Optional[Tensor], param: Tensor) -> Tuple[Tensor, Optional[Tensor]]:
+    """(the tensor a backward kernel writes the gradient of ``param`` to, what goes back to autograd): the sink, added into, and
+    ``None``; or a fresh tensor, both times."""
+    if sink is not None:
+        return sink, None
+    g = torch.empty_like(param)
+    return g, g
+
+
 def atb(a: Tensor, b: Tensor, bias: bool = False, out: Optional[Tensor] = None, bias_out: Optional[Tensor] = None,
         accumulate: bool = False, a_scale: Optional[Tensor] = None, rows_per_scale: int = 1) -> Tuple[Tensor, Optional[Tensor]]:
     """(a^T b, column sums of a) for a (K, M), b (K, N) -- the dW / db of ``y = x W^T + b`` from dY = a and X = b -- in one
@@ -1774,10 +1792,7 @@ def weight_grad(gy: Tensor, x: Tensor, w: Tensor, b: Optional[Tensor], scale: Op
     """(dW, db) of y = (x W^T + b) * scale[row // rows_per_scale] from dY (rows, out) and X (rows, in): the factor is applied
     to dY's rows as they are read, db comes out of the same pass. Inside ``grad_sinks`` both are ADDED straight into
     ``w.grad`` / ``b.grad`` and (None, None) is returned to autograd."""
-    sw = _sink(w)
-    sb = _sink(b) if (b is not None and sw is not None) else None
-    if b is not None and sb is None:
-        sw = None                                  # one accumulate flag for both: either both sinks or neither
+    sw, sb = _group_sinks(w, b)                    # one accumulate flag for both
     fn = gemm_tn if (gy.shape[0] > 0 and ((gy.shape[1] > WIDE_LAYER and x.shape[1] > WIDE_LAYER) or (gy.shape[0] >= LONG_ROWS and gy.shape[1] >= 64))) else atb
     res = fn(gy, x, bias=b is not None, out=sw, bias_out=sb, accumulate=sw is not None, a_scale=scale,
              rows_per_scale=rows_per_scale)
@@ -1922,9 +1937,8 @@ class DecoderLoopFunction(torch.autograd.Function):
             _lib.check(lib.p2c_decoder_bwd(ctypes.byref(d), _stream()), 'p2c_decoder_bwd')
         # weight gradients: dense reductions over all (t, b) at once -- library GEMMs
         g0 = gg0.view(T * B, 4 * H)
-        s0, s1, sf, sb = _sink(w_ih0), _sink(w_ih1), _sink(w_fc), _sink(b_fc)
-        if sf is None or sb is None:
-            sf = sb = None                # weight and bias of fc_out leave through one launch: both or neither
+        s0, s1 = _sink(w_ih0), _sink(w_ih1)
+        sf, sb = _group_sinks(w_fc, b_fc)     # weight and bias of fc_out leave through one launch
         g_w_ih0 = (atb(g0[B:], out[:-1].reshape(-1, O), out=s0, accumulate=s0 is not None)[0] if T > 1
                    else torch.zeros_like(w_ih0))                                            # x_0 = <sos> = 0
         g_w_ih1 = atb(gg1.view(T * B, 4 * H), h0d.view(T * B, H), out=s1, accumulate=s1 is not None)[0]
@@ -2022,12 +2036,11 @@ class DecoderStackFunction(torch.autograd.Function):
         with torch.cuda.device(out.device):
             _lib.check(lib.p2c_decoder_bwd(ctypes.byref(d), _stream()), 'p2c_decoder_bwd')
         # all weight / bias gradients: five contractions over rows, one grouped launch pair
-        sinks = {n: _sink(p) for n, p in (('w_ih0', w_ih0), ('w_hh0', w_hh0), ('b_ih0', b_ih0), ('b_hh0', b_hh0), ('w_ih1', w_ih1),
-                                          ('w_hh1', w_hh1), ('b_ih1', b_ih1), ('b_hh1', b_hh1), ('w_fc', w_fc), ('b_fc', b_fc))}
-        for group in (('w_hh0', 'b_ih0', 'b_hh0'), ('w_hh1', 'b_ih1', 'b_hh1'), ('w_fc', 'b_fc')):
-            if any(sinks[n] is None for n in group):        # a weight and its biases leave through one problem: all or none
-                for n in group:
-                    sinks[n] = None
+        params = dict(w_ih0=w_ih0, w_hh0=w_hh0, b_ih0=b_ih0, b_hh0=b_hh0, w_ih1=w_ih1, w_hh1=w_hh1, b_ih1=b_ih1, b_hh1=b_hh1,
+                      w_fc=w_fc, b_fc=b_fc)
+        sinks = {}
+        for group in (('w_ih0',), ('w_ih1',), ('w_hh0', 'b_ih0', 'b_hh0'), ('w_hh1', 'b_ih1', 'b_hh1'), ('w_fc', 'b_fc')):
+            sinks.update(zip(group, _group_sinks(*(params[n] for n in group))))   # a weight and its biases leave through one problem
 
         def prob(a, b, w, bias=None, bias2=None, with_bias=False):
             return dict(a=a, b=b, out=sinks[w], accumulate=sinks[w] is not None, bias=with_bias,
@@ -2158,11 +2171,9 @@ class EncoderStackFunction(torch.autograd.Function):
             rec(w_hh0, acts0, cs0, g_x1, 0, g_gx0, g_gx0_bt)
         names = ('w_in', 'b_in_a', 'b_in_b', 'w_hh0', 'w_ih1', 'w_hh1', 'b_ih1', 'b_hh1')
         params = dict(zip(names, (w_in, b_in_a, b_in_b, w_hh0, w_ih1, w_hh1, b_ih1, b_hh1)))
-        sinks = {n: (None if p is None else _sink(p)) for n, p in params.items()}
-        for group in (('w_in', 'b_in_a', 'b_in_b'), ('w_ih1', 'b_ih1', 'b_hh1')):
-            if any(sinks[n] is None for n in group if params[n] is not None):
-                for n in group:
-                    sinks[n] = None
+        sinks = {}
+        for group in (('w_in', 'b_in_a', 'b_in_b'), ('w_hh0',), ('w_ih1', 'b_ih1', 'b_hh1'), ('w_hh1',)):
+            sinks.update(zip(group, _group_sinks(*(params[n] for n in group))))
 
         def prob(a, b, w, bias=None, bias2=None):
             return dict(a=a, b=b, out=sinks[w], accumulate=sinks[w] is not None, bias=bias is not None,
@@ -2261,37 +2272,21 @@ class LayerNormFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, eps: float):
-        lib = _lib.lib()
         x, weight, bias = _aligned16(_require_device(x, 'x')), _require_device(weight, 'weight'), _require_device(bias, 'bias')
         D = x.shape[-1]
-        rows = x.numel() // D
-        y = torch.empty_like(x)
-        stats = torch.empty(2, rows, dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.p2c_layernorm_fwd(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), stats[0].data_ptr(),
-                                             stats[1].data_ptr(), rows, D, float(eps), _stream()), 'p2c_layernorm_fwd')
+            y, stats = _ln_fwd(x.view(x.numel() // D, D), weight, bias, eps)
         ctx.save_for_backward(x, weight, bias, stats)
-        return y
+        return y.view_as(x)
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.lib()
         x, weight, bias, stats = ctx.saved_tensors
         D = x.shape[-1]
-        rows = x.numel() // D
         gy = _aligned16(_require_device(gy, 'grad'))
-        gx = torch.empty_like(x)
-        sw, sb = _sink(weight), _sink(bias)
-        if sw is None or sb is None:
-            sw = sb = None
-        gw = sw if sw is not None else torch.empty_like(weight)
-        gb = sb if sb is not None else torch.empty_like(bias)
-        ws = torch.empty(max(1, lib.p2c_layernorm_workspace_floats(rows, D)), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.p2c_layernorm_bwd(x.data_ptr(), weight.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), gy.data_ptr(),
-                                             None, gx.data_ptr(), gw.data_ptr(), gb.data_ptr(), int(sw is not None),
-                                             ws.data_ptr(), rows, D, _stream()), 'p2c_layernorm_bwd')
-        return gx, (None if sw is not None else gw), (None if sb is not None else gb), None
+            gx, gw, gb = _ln_bwd(x.view(x.numel() // D, D), weight, bias, stats, gy, None)
+        return gx.view_as(x), gw, gb, None
 
 
 def layer_norm(x: Tensor, weight: Tensor, bias: Tensor, eps: float) -> Tensor:
@@ -2341,11 +2336,8 @@ class BatchNormActFunction(torch.autograd.Function):
         N, C = y.shape
         gz = _require_device(gz, 'grad')
         gy = torch.empty_like(y)
-        sw, sb = _sink(weight), _sink(bias)
-        if sw is None or sb is None:
-            sw = sb = None
-        gw = sw if sw is not None else torch.empty_like(weight)
-        gb = sb if sb is not None else torch.empty_like(bias)
+        sw, sb = _group_sinks(weight, bias)
+        (gw, ret_w), (gb, ret_b) = _grad_target(sw, weight), _grad_target(sb, bias)
         ws = torch.empty(max(1, lib.p2c_bnorm_workspace_floats(N, C)), dtype=torch.float32, device=y.device)
         d = _lib.BnormDesc()
         d.N, d.C, d.training, d.relu, d.accumulate = N, C, int(training), int(relu), int(sw is not None)
@@ -2354,7 +2346,7 @@ class BatchNormActFunction(torch.autograd.Function):
         d.drop_state, d.drop_p, d.drop_site = _ptr(ctx.drop_state), p, site
         with torch.cuda.device(y.device):
             _lib.check(lib.p2c_bnorm_bwd(ctypes.byref(d), ws.data_ptr(), _stream()), 'p2c_bnorm_bwd')
-        return (gy, None if sw is not None else gw, None if sb is not None else gb, gz if has_residual else None,
+        return (gy, ret_w, ret_b, gz if has_residual else None,
                 None, None, None, None, None, None, None, None, None)
 
 
@@ -2483,8 +2475,8 @@ class FrameMeanFunction(torch.autograd.Function):
         gw, _ = atb(rows, gcol)                                            # (F, 1)
         gb = column_sums(gcol)                                             # (1,)
         out_w, out_b = gw.view_as(w), gb.view_as(b)
-        sw, sb = _sink(w), _sink(b)
-        if sw is not None and sb is not None:
+        sw, sb = _group_sinks(w, b)
+        if sw is not None:
             sw.view(-1).add_(gw.view(-1)), sb.view(-1).add_(gb.view(-1))
             out_w = out_b = None
         return gx, out_w, out_b
@@ -2514,16 +2506,13 @@ def _ln_bwd(x2d: Tensor, w: Tensor, b: Tensor, stats: Tensor, gy: Tensor, gx_add
     lib = _lib.lib()
     rows, D = x2d.shape
     gx = torch.empty_like(x2d)
-    sw, sb = _sink(w), _sink(b)
-    if sw is None or sb is None:
-        sw = sb = None
-    gw = sw if sw is not None else torch.empty_like(w)
-    gb = sb if sb is not None else torch.empty_like(b)
+    sw, sb = _group_sinks(w, b)
+    (gw, ret_w), (gb, ret_b) = _grad_target(sw, w), _grad_target(sb, b)
     ws = torch.empty(max(1, lib.p2c_layernorm_workspace_floats(rows, D)), dtype=torch.float32, device=x2d.device)
     _lib.check(lib.p2c_layernorm_bwd(x2d.data_ptr(), w.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), gy.data_ptr(),
                                      _ptr(gx_add), gx.data_ptr(), gw.data_ptr(), gb.data_ptr(), int(sw is not None),
                                      ws.data_ptr(), rows, D, _stream()), 'p2c_layernorm_bwd')
-    return gx, (None if sw is not None else gw), (None if sb is not None else gb)
+    return gx, ret_w, ret_b
 
 
 def transformer_block_supported(x: Tensor, heads: int) -> bool:
@@ -2692,24 +2681,18 @@ def _postnorm_bwd(x2d: Tensor, s2d: Tensor, w: Tensor, b: Tensor, stats: Tensor,
     lib = _lib.lib()
     rows, D = x2d.shape
     gx, gs = torch.empty_like(x2d), torch.empty_like(x2d)
-    sw, sb = _sink(w), _sink(b)
-    if sw is None or sb is None:
-        sw = sb = None
-    gw = sw if sw is not None else torch.empty_like(w)
-    gb = sb if sb is not None else torch.empty_like(b)
+    sw, sb = _group_sinks(w, b)
+    (gw, ret_w), (gb, ret_b) = _grad_target(sw, w), _grad_target(sb, b)
     ws = torch.empty(max(1, lib.p2c_postnorm_workspace_floats(rows, D)), dtype=torch.float32, device=x2d.device)
     _lib.check(lib.p2c_postnorm_bwd(x2d.data_ptr(), s2d.data_ptr(), w.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
                                     gz.data_ptr(), gx.data_ptr(), gs.data_ptr(), gw.data_ptr(), gb.data_ptr(), int(sw is not None),
                                     ws.data_ptr(), rows, D, _ptr(drop_state), float(p), int(site), _stream()), 'p2c_postnorm_bwd')
-    return gx, gs, (None if sw is not None else gw), (None if sb is not None else gb)
+    return gx, gs, ret_w, ret_b
 
 
 def _wide_weight_grad(gy: Tensor, x: Tensor, w: Tensor, b: Tensor):
     """``weight_grad`` on the TN GEMM whatever the widths (the FFN's 2048-wide side is past what K12 tiles)."""
-    sw = _sink(w)
-    sb = _sink(b) if sw is not None else None
-    if sb is None:
-        sw = None
+    sw, sb = _group_sinks(w, b)
     gw, gb = gemm_tn(gy, x, out=sw, accumulate=sw is not None, bias=True, bias_out=sb)
     return (None if sw is not None else gw), (None if sb is not None else gb)
 
@@ -2847,7 +2830,7 @@ class ReluStackFunction(torch.autograd.Function):
         gy = _require_device(gy, 'grad')
         B, T = x.shape[:2]
         desc = _relu_stack_desc(ctx.dims, B, T, ctx.flip)
-        sinks = [_sink(p) for p in ctx.params]
+        sinks = _group_sinks(*ctx.params)
         if any(s is None or not s.is_contiguous() for s in sinks):
             sinks = None
         if sinks is not None:

@@ -904,3 +904,46 @@ def test_contiguous_operands_come_back_as_the_same_object(lifetimes):
     prob = OPS['lstm_k18']()
     run(prob, prob.layouts('contiguous'), False)
     assert lifetimes.same_object >= 6 and not lifetimes.pending and not lifetimes.drain()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# grad sinks with a mixed group: one parameter of a layer has a prefilled .grad, the other has none
+# ----------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _sink_problem(op):
+    """(call, x, weight, bias, upstream gradient, gradient of weight, gradient of bias) on the device; the two gradients come from
+    one call outside ``grad_sinks``. layer_norm: 37 rows leave a partly filled workgroup pass and D = 12 leaves five of a row's
+    eight lanes without a column; dense: 5 rows, 12 -> 7."""
+    from pedestrians_video_2_carla_amd import ops
+    d, g = dev(), _g(37)
+    if op == 'layer_norm':
+        x, w, b, up = _randn(g, 37, 12), 1 + _randn(g, 12, scale=0.1), _randn(g, 12, scale=0.1), _randn(g, 37, 12)
+        call = lambda x, w, b: ops.layer_norm(x, w, b, 1e-5)      # noqa: E731
+    else:
+        x, w, b, up = _randn(g, 5, 12), _randn(g, 7, 12), _randn(g, 7), _randn(g, 5, 7)
+        call = ops.dense
+    x, w, b, up = (t.float().to(d) for t in (x, w, b, up))
+    pw, pb = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    (call(x, pw, pb) * up).sum().backward()
+    return call, x, w, b, up, pw.grad.clone(), pb.grad.clone()
+
+
+@pytest.mark.parametrize('prefilled', ['weight', 'bias', 'both'])
+@pytest.mark.parametrize('op', ['layer_norm', 'dense'])
+def test_grad_sinks_with_a_mixed_group(op, prefilled):
+    """Inside ``grad_sinks`` a layer whose weight has a ``.grad`` and whose bias has none (or the reverse) must leave what
+    autograd leaves: prefill + gradient where a ``.grad`` stood, the gradient where none did. Either way the last operation is
+    one fp32 add of the same two numbers, so the bits are equal."""
+    from pedestrians_video_2_carla_amd import ops
+    call, x, w, b, up, gw, gb = _sink_problem(op)
+    pw, pb = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    fill_w, fill_b = torch.full_like(w, 0.375) + w, torch.full_like(b, -1.25) + b
+    if prefilled in ('weight', 'both'):
+        pw.grad = fill_w.clone()
+    if prefilled in ('bias', 'both'):
+        pb.grad = fill_b.clone()
+    with ops.grad_sinks(True):
+        (call(x, pw, pb) * up).sum().backward()
+    torch.cuda.synchronize()
+    assert torch.equal(pw.grad, fill_w + gw if prefilled in ('weight', 'both') else gw)
+    assert torch.equal(pb.grad, fill_b + gb if prefilled in ('bias', 'both') else gb)
