@@ -316,6 +316,7 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   auto one_clip = [&](const int clip, int st, auto first_c) {
   constexpr bool first = decltype(first_c)::value;
   PL.clip = clip;
+  const __amdgpu_buffer_rsrc_t frs = factor_rsrc(m.factors, clip);   // this clip's factor block (factor_store)
   if constexpr (!first) lds_barrier();        // the previous clip's factor store / loss sums have consumed H, G and scratch
   // Every lane loads UNCONDITIONALLY from a clamped (always valid) address and selects afterwards: a load inside a divergent
   // branch makes the compiler wait for it (and for every older load) at the branch's end.
@@ -501,10 +502,35 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   TT(0, 13);
   // Steps 3 and 2 (n_in = 6 and 13) are one m-tile each, both on wave 0: one run behind step 3's barrier, wave-local sync between.
   static_assert(S::dims(3) <= 16 && S::dims(2) <= 16, "dgrad steps 3 and 2: one m-tile each");
+#if P2C_TRAIN_FACTOR_EARLY
+  // The next clip's x tile arrived during the forward. Its wait is taken here, in front of the first factor store: left to the top of
+  // the next clip it would be a wait for this clip's stores as well (see below).
+#pragma unroll
+  for (int u = 0; u < TILE_UV; ++u) asm volatile("" : "+v"(xr.v[u]));
+#endif
   for_layers_down(sh, nl - 1, 1, [&](int ll) {
     if (ll == 2) lds_wave_sync();
     else lds_barrier();
     TT(0, 14 + ll);
+#if P2C_TRAIN_FACTOR_EARLY
+    // The G segment(s) this barrier published, from the waves that have no m-tile in this step (layer_dgrad deals 5 / 3 / 1 / 1 / 2
+    // tiles to waves 0 ..): G_6 (624 items) beside step 5, G_5 (312) beside step 4, G_4 (156) beside wave 0's run of steps 3 -> 2,
+    // G_3 and G_2 (76, written inside that run: published by step 1's barrier, not before) beside step 1. Scan plane 1 aliased the
+    // rows of G_1 .. G_5 during the pose phase: each is read only behind the barrier that follows the dgrad step that wrote it.
+    // The H half (856 items, final since the forward) goes with G_6, the longest step: nine rounds on three waves. It does NOT
+    // leave during the forward or the pose phase. Stores count in vmcnt with the loads and retire in order, and the waves carry
+    // different numbers of them, so the compiler's next wait for a load, wherever it stands behind a store site, is vmcnt(0) =
+    // a wait for that wave's write-through stores: the image rounds (first clip) and the pose phase's world and target reads
+    // would put it on every wave's path. From here to the clip's end no wave waits for a load.
+    if (ll == 5) {
+      factor_store<F_SEGS - 1, F_SEGS, 5, WAVES>(H, frs, L.wave, L.lane);
+      factor_store<0, NLAY, 5, WAVES>(H, frs, L.wave, L.lane);
+    }
+    if (ll == 4) factor_store<F_SEGS - 2, F_SEGS - 1, 3, WAVES>(H, frs, L.wave, L.lane);
+    if (ll == 3) factor_store<F_SEGS - 3, F_SEGS - 2, 1, WAVES>(H, frs, L.wave, L.lane);
+    if (ll == 1) factor_store<NLAY + 1, NLAY + 3, 2, WAVES>(H, frs, L.wave, L.lane);
+    static_assert(NLAY == 6 && WAVES == 8, "the early store schedule is read off this shape's tile dealing");
+#endif
     layer_dgrad<P2C_PREC_F32, true>(L, lds + S::w_off(ll), S::ld(ll), S::dims(ll), S::dims(ll + 1), G + S::h_off(ll + 1) * TP, H + S::h_off(ll) * TP,
                 G + S::h_off(ll) * TP);
   });
@@ -515,32 +541,25 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   TT(0, 20);
 
   // ---- the clip's factors, as they sit in LDS (transposed, 16 samples = 64 B per row) ----
-  f32x4 *fdst = reinterpret_cast<f32x4 *>(m.factors) + (size_t)clip * F_ROWS * 4;
-  // One batch: every LDS read of the thread first (item i = this thread's k-th sixteen bytes of the dense block, taken from the
-  // padded row that holds factor row i / 4), then the stores back to back. Twelve per-segment loops were thirteen dependent rounds of
-  // address arithmetic, LDS read, wait, store and a mask branch; the block is contiguous in memory, so five rounds cover it.
+  // One batch per wave (factor_store): every LDS read of the lane first, then the stores back to back. Twelve per-segment loops were
+  // thirteen dependent rounds of address arithmetic, LDS read, wait, store and a mask branch; the block is contiguous in memory.
+  // With the early placement only G_1 (104 items, waves 0 and 1) is left for this place: the other segments left from idle waves
+  // behind the barriers that published them, write-through, so the kernel's end finds none of them dirty in L2.
   // The loss partials of the clip ride along: wave 0 reads the 24 per-wave sums in the same LDS trip and adds them in wave order
   // once its stores are out.
-  constexpr int F_ITEMS = F_ROWS * 4, F_ROUNDS = (F_ITEMS + NTH - 1) / NTH;
-  f32x4 fv[F_ROUNDS];
-#pragma unroll
-  for (int k = 0; k < F_ROUNDS; ++k) {
-    int i = threadIdx.x + k * NTH;
-    if ((k + 1) * NTH > F_ITEMS) i = i < F_ITEMS ? i : F_ITEMS - 1;       // (the last round is partial: read a valid row, store nothing)
-    const int hi = ((k + 1) * NTH - 1) >> 2;
-    const int o = f_lds_row(i >> 2, (k * NTH) >> 2, hi < F_ROWS ? hi : F_ROWS - 1) * TP + (i & 3) * 4;
-    fv[k] = (f32x4){H[o], H[o + 1], H[o + 2], H[o + 3]};
-  }
   float rv[3 * WAVES];
   if (L.wave == 0) {
 #pragma unroll
     for (int i = 0; i < 3 * WAVES; ++i) rv[i] = red[i];
   }
-#pragma unroll
-  for (int k = 0; k < F_ROUNDS; ++k) {
-    const int i = threadIdx.x + k * NTH;
-    if ((k + 1) * NTH <= F_ITEMS || i < F_ITEMS) fdst[i] = fv[k];
-  }
+#if P2C_TRAIN_FACTOR_EARLY
+  factor_store<NLAY, NLAY + 1, 0, 2>(H, frs, L.wave, L.lane);
+#elif P2C_TRAIN_FACTOR_SC1 == 2
+  factor_store<0, NLAY, 0, WAVES>(H, frs, L.wave, L.lane);
+  factor_store<NLAY, F_SEGS, 0, WAVES>(H, frs, L.wave, L.lane);
+#else
+  factor_store<0, F_SEGS, 0, WAVES>(H, frs, L.wave, L.lane);
+#endif
   if (L.wave == 0) {
     float a = 0.f, b = 0.f, cc = 0.f;
 #pragma unroll
@@ -561,7 +580,9 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
 // ---- second launch: weight gradient over all clips + optimizer + loss reduction ------------------------------------------
 // Split-K over ALL CUs with an in-launch combine. Workgroup (t, q) -- q = blockIdx % 8, consecutive workgroups land on
 // consecutive XCDs -- owns dW tile t and the clips st = q (mod 8): the ones train_clip_kernel's workgroups on the SAME XCD
-// wrote a moment ago (speed only: plain stores keep the lines in that XCD's L2). Wave w walks clips q + 8 w, + 64, ... with
+// wrote a moment ago (speed only: plain stores kept the lines in that XCD's L2; the write-through stores the clip kernel uses now
+// drop them there, and this launch's duration in the kernel trace went from 9.3 to 9.5 us for 1.0 us less of the first launch's:
+// DESIGN 5.20). Wave w walks clips q + 8 w, + 64, ... with
 // one accumulator, the eight waves are added in w order through LDS (= mlp_wgrad_kernel). The slice's partial tile is
 // PUBLISHED with write-through (sc1) stores; the workgroup whose ticket on the tile's counter is the last one reads the
 // eight slices back with sc1 loads, adds them in q order (fixed: not arrival order -> bitwise reproducible and identical

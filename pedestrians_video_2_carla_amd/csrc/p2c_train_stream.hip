@@ -298,6 +298,16 @@ template <int ROWS>
 __device__ __forceinline__ void half_read(const float *src, const int lane, const int half, HalfRows<ROWS> &h);
 template <int ROWS>
 __device__ __forceinline__ void half_store(const HalfRows<ROWS> &h, float *dst, const int lane, const int half);
+// The factor rows' store instruction: write-through (sc1) like train_clip_kernel's; EXTRA=-DP2C_STREAM_FACTOR_SC1=0 (p2c_train_dev.h)
+// gives the plain stores back. At B = 1 024 the blocks (35 MB) are about the size of all eight L2s and the plain stores' dirty lines
+// were written back at the kernel's end: tools/step_sweep.py, first launch 33.0 -> 30.6 us, the second unchanged (18.4 us: it is
+// bandwidth-bound and did not read these lines from L2 anyway), step 51.5 - 52.2 -> 50.9 - 51.0 us; B = 8 192 201 -> 199 us of 276
+// (profiles/k13_handoff).
+#if P2C_STREAM_FACTOR_SC1
+#define P2C_STREAM_FACTOR_STORE "global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1"
+#else
+#define P2C_STREAM_FACTOR_STORE "global_store_dwordx4 %0, %1, off\n\ts_nop 1"
+#endif
 template <int ROWS>
 __device__ __forceinline__ void rows_read(const float *src, const int lane, RowRegs<ROWS> &r) {
   const f32x4 *s4 = reinterpret_cast<const f32x4 *>(src);
@@ -317,7 +327,7 @@ __device__ __forceinline__ void rows_store(const RowRegs<ROWS> &r, float *dst, c
     // completion (vmcnt) -- with 34 KB of factors per clip in flight the MLP wave drained its queue a dozen times per clip.
     // The hardware needs two wait states, inside the string (cdna_hip_programming.md, inline-asm rules: stores).
     if (!(P2C_STREAM_EXPERIMENT & 4) && ((i + 1) * 64 <= ROWS * 4 || p < ROWS * 4))
-      asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(d4 + p), "v"(r.v[i]) : "memory");
+      asm volatile(P2C_STREAM_FACTOR_STORE ::"v"(d4 + p), "v"(r.v[i]) : "memory");
   }
 }
 
@@ -340,7 +350,7 @@ __device__ __forceinline__ void half_store(const HalfRows<ROWS> &h, float *dst, 
 #pragma unroll
   for (int i = 0; i < (RM * 4 + 63) / 64; ++i) {
     const int p = i * 64 + lane;
-    if (!(P2C_STREAM_EXPERIMENT & 4) && p < n4) asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(d4 + p), "v"(h.r.v[i]) : "memory");
+    if (!(P2C_STREAM_EXPERIMENT & 4) && p < n4) asm volatile(P2C_STREAM_FACTOR_STORE ::"v"(d4 + p), "v"(h.r.v[i]) : "memory");
   }
 }
 
