@@ -1621,17 +1621,40 @@ def _grad_target(sink: Optional[Tensor], param: Tensor) -> Tuple[Tensor, Optiona
     return g, g
 
 
+def _atb_no_rows(M: int, N: int, device, bias: bool, out: Optional[Tensor], bias_out: Optional[Tensor],
+                 bias_out2: Optional[Tensor], accumulate: bool) -> Tuple[Tensor, Optional[Tensor]]:
+    """What p2c_atb leaves for K = 0, without a launch (a tensor without elements has no address to hand over): an empty sum
+    is zero, so an output that is overwritten becomes zeros and one that is added into stays as it is. The flags are those of
+    ``atb``: ``out`` is added into under ``accumulate``, the bias vectors only if ``bias_out`` was given as well."""
+    if out is None:
+        out = torch.zeros(M, N, dtype=torch.float32, device=device)
+    elif not accumulate:
+        out.zero_()
+    if not bias:
+        return out, None
+    keep_bias = accumulate and bias_out is not None
+    if bias_out is None:
+        bias_out = torch.zeros(M, dtype=torch.float32, device=device)
+    elif not keep_bias:
+        bias_out.zero_()
+    if bias_out2 is not None and not keep_bias:
+        bias_out2.zero_()
+    return out, bias_out
+
+
 def atb(a: Tensor, b: Tensor, bias: bool = False, out: Optional[Tensor] = None, bias_out: Optional[Tensor] = None,
         accumulate: bool = False, a_scale: Optional[Tensor] = None, rows_per_scale: int = 1) -> Tuple[Tensor, Optional[Tensor]]:
     """(a^T b, column sums of a) for a (K, M), b (K, N) -- the dW / db of ``y = x W^T + b`` from dY = a and X = b -- in one
     launch (p2c_atb). Rows may be strided views (row pitch = stride(0), unit column stride). ``a_scale``: row k of a is
-    multiplied by ``a_scale[k // rows_per_scale]`` as it is read."""
+    multiplied by ``a_scale[k // rows_per_scale]`` as it is read. K = 0 is answered on the host (``_atb_no_rows``)."""
     lib = _lib.lib()
     a, b = (t if (t.is_cuda and t.dtype == torch.float32 and t.stride(-1) == 1) else _require_device(t, 'operand') for t in (a, b))
     K, M, N = a.shape[0], a.shape[1], b.shape[1]
     if b.shape[0] != K:
         raise RuntimeError('atb: row counts differ')
     a_scale = None if a_scale is None else _require_device(a_scale, 'a_scale')       # the kernel reads it with unit stride
+    if K == 0:
+        return _atb_no_rows(M, N, a.device, bias, out, bias_out, None, accumulate)
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=a.device)
     flags = (1 if accumulate else 0) | (2 if (accumulate and bias_out is not None) else 0)   # a fresh bias vector is overwritten
@@ -1663,14 +1686,12 @@ def atb_group(problems: Sequence[dict]) -> list:
             if pr['a'].shape[0] > 0:
                 results.append(next(done))
                 continue
-            M, N = pr['a'].shape[1], pr['b'].shape[1]
+            if pr['b'].shape[0] != 0:
+                raise RuntimeError('atb_group: row counts differ')
             out = pr.get('out')
-            if out is None:
-                out = torch.zeros(M, N, dtype=torch.float32, device=pr['a'].device)
-            bias_out = pr.get('bias_out')
-            if pr.get('bias', False) and bias_out is None:
-                bias_out = torch.zeros(M, dtype=torch.float32, device=pr['a'].device)
-            results.append((out, bias_out if pr.get('bias', False) else None))
+            results.append(_atb_no_rows(pr['a'].shape[1], pr['b'].shape[1], pr['a'].device, bool(pr.get('bias', False)), out,
+                                        pr.get('bias_out'), pr.get('bias_out2'),
+                                        bool(pr.get('accumulate', False)) and out is not None))
         return results
     arr = (_lib.AtbProblem * n)()
     keep, results = [], []
