@@ -276,6 +276,14 @@ P2C_API int p2c_train_step_set_stream_min_batch(int32_t min_b);
  * persistent workgroup per clip slice that reads every factor block once and holds all 79 tiles, followed by a third launch
  * that adds the per-workgroup partials in a fixed order (+ optimizer + losses). Returns the previous threshold. */
 P2C_API int p2c_train_step_set_wgrad_stream_min_batch(int32_t min_b);
+/* The latency form of the first launch is compiled twice per 6-D kind. One instantiation reads every descriptor field at run
+ * time. The other is specialised for ONE descriptor state, the reference's default pose-lifting configuration: transform
+ * hips_neck_bbox with n_hips = n_neck = 1, dloc = drot = NULL, identity gmap2d / gmap3d, gt2d and gt3d present, t0 = 0,
+ * t1 = T = 16, mask_missing_joints = 1. Same arithmetic, same bits; every other descriptor runs the general one.
+ * p2c_train_step_set_specialized(on) switches the specialised instantiation on (default) or off and returns the previous
+ * value; on < 0 only queries. p2c_train_step_specialized(desc) = 1 if the descriptor is in that state, else 0. */
+P2C_API int p2c_train_step_set_specialized(int32_t on);
+P2C_API int p2c_train_step_specialized(const p2c_train_step_desc *desc);
 /* counts[b] = number of (frame, joint) pairs of clip b inside [t0, t1) whose 2-D target the loss does not mask
  * (utils/tensors.py:29-40 via loss/base_pose_loss.py:36-66): reads only the target-side fields of desc (gt2d, gmap2d,
  * hips_lane, mask_missing_joints, t0, t1); y / partials / losses may be NULL. One launch. */

@@ -329,6 +329,8 @@ SYMBOLS = {
     'p2c_count_target_pairs': (ctypes.c_int, [ctypes.POINTER(PoseHeadDesc), _vp, _vp]),
     'p2c_train_step_set_stream_min_batch': (ctypes.c_int, [ctypes.c_int32]),
     'p2c_train_step_set_wgrad_stream_min_batch': (ctypes.c_int, [ctypes.c_int32]),
+    'p2c_train_step_set_specialized': (ctypes.c_int, [ctypes.c_int32]),
+    'p2c_train_step_specialized': (ctypes.c_int, [ctypes.POINTER(TrainStepDesc)]),
     'p2c_relu_stack_supported': (ctypes.c_int, [ctypes.POINTER(ReluStackDesc)]),
     'p2c_relu_stack_workspace_floats': (_i64, [ctypes.POINTER(ReluStackDesc)]),
     'p2c_relu_stack_fwd': (ctypes.c_int, [ctypes.POINTER(ReluStackDesc), _vp]),

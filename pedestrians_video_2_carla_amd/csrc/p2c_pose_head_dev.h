@@ -301,6 +301,11 @@ struct HeadAcc {
 
 enum { MODE_FWD = 0, MODE_FWD_MATERIALIZE = 1, MODE_BWD = 2, MODE_TRAIN = 3 };   // TRAIN = BWD that also sums the losses
 
+// 1 / (number of joints averaged into the hips or the neck point), as frame_head's backward multiplies by it. A descriptor type
+// whose count is a compile-time constant gives the field a type of its own and an overload of this beside it (train_clip_kernel's
+// CFG_DEFAULT: the product must stay a product, see there).
+__device__ __forceinline__ float inv_count(int32_t n) { return 1.f / (float)n; }
+
 // D: p2c_pose_head_desc, or a caller's own copy of the fields read here (train_clip_kernel: PoseConsts, fetched in one batch).
 template <int MODE, class D>
 __device__ __forceinline__ V3 frame_head(const D &d, const LaneCtx &L, int t, V3 x, const World &W,
@@ -471,11 +476,11 @@ __device__ __forceinline__ V3 frame_head(const D &d, const LaneCtx &L, int t, V3
       float r = (hn_scale > 0.f) ? g_scale * frcp(hn_scale) : 0.f;
       float gku = r * (ku - hu), gkv = r * (kv - hv);
       gsu -= gku, gsv -= gkv;
-      float kn = 1.f / (float)d.n_neck;
+      float kn = inv_count(d.n_neck);
       if (L.j == d.neck_idx[0] || (d.n_neck == 2 && L.j == d.neck_idx[1])) gu += gku * kn, gv += gkv * kn;
     }
     if (tr != P2C_TRANSFORM_BBOX) {
-      float hn = 1.f / (float)d.n_hips;
+      float hn = inv_count(d.n_hips);
       if (L.j == d.hips_idx[0] || (d.n_hips == 2 && L.j == d.hips_idx[1])) gu += gsu * hn, gv += gsv * hn;
     }
     if (tr == P2C_TRANSFORM_BBOX || __any(use_bb_scale)) {

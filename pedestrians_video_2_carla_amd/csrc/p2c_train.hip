@@ -138,6 +138,50 @@ struct PoseConsts {
   float near_zero, cam_f, cam_cx, cam_cy, cam_dist, cam_elev;
   gcfloat *dloc, *drot;
 };
+// Two instantiations of train_clip_kernel per 6-D kind. CFG_GENERIC reads every field above at run time. CFG_DEFAULT
+// covers ONE descriptor state, the reference's default pose-lifting configuration (clip_is_default below decides on the host):
+// hips_neck_bbox with one hips and one neck joint, no world motion, identity joint maps, both targets present, the whole clip in
+// the slice, T = 16, masked missing joints. There the fields that state fixes are compile-time constants: ph::frame_head and
+// ph::world_at take the descriptor type as a template argument and fold their branches on them as they stand, and nothing of
+// them occupies an SGPR. What stays in registers: near_zero, the camera, the first hips / neck index, B. The bounding-box
+// fallback depends on the data (__any(need_bb)) and stays a branch.
+enum { CFG_GENERIC = 0, CFG_DEFAULT = 1 };
+// Bit for bit means the same ROUNDINGS, and hipcc contracts a product into a following add (a * b + c -> fma) wherever the product
+// is visible to the add. Two places of ph::frame_head's backward owe a rounding to a run-time field, and CFG_DEFAULT keeps both:
+//   * gu += gku * (1 / n_neck), gv, and the same with n_hips. With the factor folded to 1 the product gku = r * (ku - hu) in front
+//     of it would be contracted into the add. `One` compares as the constant 1 (the n == 2 branches fold) and hands ph::inv_count
+//     a 1.0f the optimiser cannot see through: the multiplication stays, as an fma with an SGPR operand.
+//   * gx + (W.on ? gp W.rot^T : gp). With W.on folded to false the three products of gp would be contracted into the add.
+//     default_world() below hands frame_head a World whose `on` is a false it cannot see through (a scalar branch each way).
+struct One {
+  __device__ constexpr bool operator==(int v) const { return v == 1; }
+};
+__device__ __forceinline__ float inv_count(One) {
+  float one = 1.f;
+  asm volatile("" : "+s"(one));
+  return one;
+}
+struct PoseConstsDefault {
+  static constexpr int32_t T = T_MAX, t0 = 0, t1 = T_MAX, transform = P2C_TRANSFORM_HIPS_NECK_BBOX, mask_missing_joints = 1,
+                           world_absolute = 0;
+  static constexpr One n_hips{}, n_neck{};
+  static constexpr const float *dloc = nullptr, *drot = nullptr;
+  int32_t B, hips_idx[2], neck_idx[2];      // ([1] of either: never read, n_hips = n_neck = 1)
+  float near_zero, cam_f, cam_cx, cam_cy, cam_dist, cam_elev;
+};
+__device__ __forceinline__ ph::World default_world() {
+  int on = 0;
+  asm volatile("" : "+s"(on));
+  return ph::World{ph::identity(), ph::v3(0.f, 0.f, 0.f), on != 0};
+}
+template <int CFG>
+struct PoseConstsOf {
+  typedef PoseConsts type;
+};
+template <>
+struct PoseConstsOf<CFG_DEFAULT> {
+  typedef PoseConstsDefault type;
+};
 // inclusive scan over the frames of the clip, P_t = c_t c_{t-1} ... c_0 (the order of p2c::scan_time), ping-pong planes
 __device__ __forceinline__ ph::M3 scan_time2(ph::M3 P, int t, int j, int T, float *p0, float *p1) {
   float *cur = p0, *oth = p1;
@@ -204,11 +248,12 @@ __device__ __forceinline__ void image_dma_wait(int l, int wave) {
   }
 }
 
-template <int KIND>
+template <int KIND, int CFG>
 __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_head_desc d, const ph::GradLosses gl,
                                                                 const ClipArgs m) {
   using K = ph::KindTraits<KIND>;
   static_assert(K::SIXD, "the fused step is for the 6-D kinds");
+  constexpr bool DEF = CFG == CFG_DEFAULT;     // the descriptor state of PoseConstsDefault: its fixed fields are not read
   extern __shared__ float lds[];
   const S sh;
   Lane L;
@@ -221,7 +266,7 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   float *Y = G + S::h_off(nl) * TP;                        // y^T, later grad_y^T (= G_L)
   float *plane0 = H + ACT_FLOATS, *plane1 = G + S::h_off(1) * TP;
   float *scratch = plane0 + PLANE;
-  const int T = d.T;
+  const int T = DEF ? T_MAX : d.T;
   TT(0, 0);
 
   // ---- clip-independent set-up --------------------------------------------------------------------------------------------------
@@ -251,14 +296,14 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   PL.lane = threadIdx.x & 63, PL.j = PL.lane & 31, PL.base = PL.lane & 32, PL.clip = blockIdx.x;
   const int t = (int)(threadIdx.x >> 6) * 2 + (PL.lane >> 5);
   PL.active = (PL.j < ph::J) && (t < T);
-  if (m.identity_maps) {
+  if (DEF || m.identity_maps) {
     PL.anc0 = ph::c_parent[PL.j], PL.anc1 = ph::c_anc_r2[PL.j], PL.anc2 = ph::c_anc_r3[PL.j];
     PL.interior = (ph::kInteriorMask >> PL.j) & 1u;
     PL.sub_end = ph::c_subtree_end[PL.j];
     PL.gm2 = PL.gm3 = (PL.j < ph::J) ? PL.j : -1;
     PL.never_masked = (PL.j == d.hips_lane);
-    PL.has2 = PL.active && d.gt2d;
-    PL.has3 = PL.active && d.gt3d;
+    PL.has2 = PL.active && (DEF || d.gt2d);
+    PL.has3 = PL.active && (DEF || d.gt3d);
   } else {
     ph::fill_lane(PL, d);
   }
@@ -307,8 +352,8 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
     if (gl.p[0] || gl.p[1] || gl.p[2]) {
       const float u0 = gl.p[0] ? uraw[0] : 0.f, u1 = gl.p[1] ? uraw[1] : 0.f, u2 = gl.p[2] ? uraw[2] : 0.f;
       const float g2 = u0 + u2, g3 = u1 + u2, n3 = m.n3_elems;
-      k2 = (d.gt2d && n2 > 0.f) ? g2 / n2 : 0.f;
-      k3 = (d.gt3d && n3 > 0.f) ? 2.f * g3 / n3 : 0.f;
+      k2 = ((DEF || d.gt2d) && n2 > 0.f) ? g2 / n2 : 0.f;
+      k3 = ((DEF || d.gt3d) && n3 > 0.f) ? 2.f * g3 / n3 : 0.f;
     }
     if (L.lane == 0) scratch[0] = k2, scratch[1] = k3;
   };
@@ -325,7 +370,7 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   float g2raw[2], g3raw[3];
   {
     const size_t frame = (size_t)clip * T + tc;
-    const float *b2 = d.gt2d ? d.gt2d : d.ref_rel_loc, *b3 = d.gt3d ? d.gt3d : d.ref_rel_loc;   // any readable address
+    const float *b2 = (DEF || d.gt2d) ? d.gt2d : d.ref_rel_loc, *b3 = (DEF || d.gt3d) ? d.gt3d : d.ref_rel_loc;   // any readable address
     const float *p2 = b2 + (PL.has2 ? (frame * d.gt2d_joints + PL.gm2) * d.gt2d_channels : 0);
     const float *p3 = b3 + (PL.has3 ? (frame * d.gt3d_joints + PL.gm3) * 3 : 0);
     g2raw[0] = p2[0], g2raw[1] = p2[1];
@@ -343,7 +388,7 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   // rounds of layer 2 are therefore committed in front of layer 1's barrier.
   static_assert(S::dims(2) + 1 <= 16 && S::dims(3) + 1 <= 16, "layers 1 and 2: one output tile each");
   static_assert(rounds_upto<S>(2) <= issue_mark<S>(2), "layer 2's image rounds are in flight before layer 1's barrier commits them");
-  PoseConsts pc;
+  typename PoseConstsOf<CFG>::type pc;
   for_layers(sh, 0, nl, [&](int ll) {
     const bool run = ll == 2;           // second layer of the single-wave run: no workgroup barrier
 #if P2C_TRAIN_DMA_IMAGE
@@ -379,7 +424,13 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
       for (int i = 0; i < 9; ++i) rraw[i] = K::SCAN ? pr[i] : 0.f;
     }
     const bool last = (ll == nl - 1);
-    if (last) {   // the pose phase's descriptor fields: one batch, in flight under the last layer's MFMA chain
+    if constexpr (DEF) {
+      if (last) {   // what the configuration does not fix: the same one batch
+        pc = PoseConstsDefault{d.B, {d.hips_idx[0], 0}, {d.neck_idx[0], 0}, d.near_zero, d.cam_f, d.cam_cx, d.cam_cy, d.cam_dist, d.cam_elev};
+        asm volatile("" : "+s"(pc.B), "+s"(pc.hips_idx[0]), "+s"(pc.neck_idx[0]), "+s"(pc.near_zero), "+s"(pc.cam_f), "+s"(pc.cam_cx),
+                     "+s"(pc.cam_cy), "+s"(pc.cam_dist), "+s"(pc.cam_elev));
+      }
+    } else if (last) {   // the pose phase's descriptor fields: one batch, in flight under the last layer's MFMA chain
       pc = PoseConsts{d.B, d.T, d.t0, d.t1, d.transform, d.n_hips, d.n_neck, {d.hips_idx[0], d.hips_idx[1]}, {d.neck_idx[0], d.neck_idx[1]},
                     d.mask_missing_joints, d.world_absolute, d.near_zero, d.cam_f, d.cam_cx, d.cam_cy, d.cam_dist, d.cam_elev,
                     (PoseConsts::gcfloat *)d.dloc, (PoseConsts::gcfloat *)d.drot};
@@ -418,7 +469,9 @@ __global__ __launch_bounds__(64 * WAVES) void train_clip_kernel(const p2c_pose_h
   ph::M3 A = R;
   ph::V3 x = l;
   ph::fk_doubling(PL, A, x);
-  const ph::World W = ph::world_at(pc, PL, t);
+  ph::World W;
+  if constexpr (DEF) W = default_world();
+  else W = ph::world_at(pc, PL, t);
   ph::HeadAcc acc{0.f, 0.f, 0.f};
   ph::V3 F = ph::frame_head<ph::MODE_TRAIN>(pc, PL, t, x, W, acc, coef2, coef3, nullptr, nullptr, g2, g3);
   TT(0, 10);
@@ -1118,6 +1171,28 @@ extern "C" P2C_API int p2c_train_step_set_stream_min_batch(int32_t min_b) {
   return prev;
 }
 
+// ---- which instantiation of train_clip_kernel a descriptor takes -------------------------------------------------------------
+static int identity_maps(const p2c_pose_head_desc &d) {
+  int identity = 1;
+  for (int j = 0; j < P2C_JOINTS; ++j) identity &= (d.gmap2d[j] == j) && (d.gmap3d[j] == j);
+  return identity;
+}
+// the one descriptor state CFG_DEFAULT is compiled for (PoseConstsDefault), field by field
+static bool clip_is_default(const p2c_pose_head_desc &d, int identity) {
+  return d.transform == P2C_TRANSFORM_HIPS_NECK_BBOX && d.n_hips == 1 && d.n_neck == 1 && !d.dloc && !d.drot && identity &&
+         d.gt2d && d.gt3d && d.t0 == 0 && d.t1 == d.T && d.T == T_MAX && d.mask_missing_joints == 1;
+}
+static int g_specialized = 1;    // off: every descriptor runs CFG_GENERIC (A/B timing, tests/test_clip_pose_spec_gpu.py)
+extern "C" P2C_API int p2c_train_step_set_specialized(int32_t on) {
+  const int prev = g_specialized;
+  if (on >= 0) g_specialized = on ? 1 : 0;
+  return prev;
+}
+extern "C" P2C_API int p2c_train_step_specialized(const p2c_train_step_desc *desc) {
+  if (!p2c_train_step_supported(desc)) return 0;
+  return clip_is_default(desc->head, identity_maps(desc->head)) ? 1 : 0;
+}
+
 static constexpr int kClipBlocks = 256;   // CUs of an MI355X: one 156 KB-LDS workgroup each
 static constexpr int kTilesW = 79;    // 16x16 tiles of the augmented weight gradients of LinearAE156 (checked below)
 // workspace: [factors (B, F_ROWS, 16) | slices (KS, tiles, 256) | counters (tiles, padded to 128 ints)]
@@ -1181,9 +1256,12 @@ extern "C" int p2c_train_step_launch(const p2c_train_step_desc *desc, const floa
   }
   hipStream_t stream = (hipStream_t)stream_;
   static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void *)train_clip_kernel<P2C_KIND_POSE_CHANGES_6D>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void *)train_clip_kernel<P2C_KIND_RELATIVE_ROT_6D>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (!attr_done) {   // every instantiation: without it the launch of a 156 KB-LDS workgroup fails
+    const void *const clip_kernels[] = {(const void *)train_clip_kernel<P2C_KIND_POSE_CHANGES_6D, CFG_GENERIC>,
+                                        (const void *)train_clip_kernel<P2C_KIND_RELATIVE_ROT_6D, CFG_GENERIC>,
+                                        (const void *)train_clip_kernel<P2C_KIND_POSE_CHANGES_6D, CFG_DEFAULT>,
+                                        (const void *)train_clip_kernel<P2C_KIND_RELATIVE_ROT_6D, CFG_DEFAULT>};
+    for (const void *k : clip_kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done = true;
   }
   if (!m.skip_pack && (which & 1)) {
@@ -1198,8 +1276,7 @@ extern "C" int p2c_train_step_launch(const p2c_train_step_desc *desc, const floa
   if (tiles != kTilesW) return P2C_E_SHAPE;
   float *slices = m.partials + (size_t)d.B * F_ROWS * 16;
   int32_t *counters = reinterpret_cast<int32_t *>(slices + (size_t)WS_BLOCKS_MAX * kTilesW * 256);
-  int identity = 1;
-  for (int j = 0; j < P2C_JOINTS; ++j) identity &= (d.gmap2d[j] == j) && (d.gmap3d[j] == j);
+  const int identity = identity_maps(d);
   const float n3_elems = (float)((double)d.B * (double)(d.t1 - d.t0) * (double)d.n_common3d * 3.0);   // = ph::n3_elems(d)
   ClipArgs ca{m.x, m.w_image, desc->pair_counts, m.partials, counters, tiles, identity, n3_elems};
   const size_t lds_a = (size_t)LDS_FLOATS * sizeof(float);
@@ -1210,10 +1287,11 @@ extern "C" int p2c_train_step_launch(const p2c_train_step_desc *desc, const floa
     rc = p2c_internal_train_stream_launch(d, gl, ca, stream);
     if (rc) return rc;
   } else if (which & 1) {
-    if (d.kind == P2C_KIND_POSE_CHANGES_6D)
-      hipLaunchKernelGGL(train_clip_kernel<P2C_KIND_POSE_CHANGES_6D>, grid_a, dim3(64 * WAVES), lds_a, stream, d, gl, ca);
-    else
-      hipLaunchKernelGGL(train_clip_kernel<P2C_KIND_RELATIVE_ROT_6D>, grid_a, dim3(64 * WAVES), lds_a, stream, d, gl, ca);
+    const bool def = g_specialized && clip_is_default(d, identity);
+    auto *const kernel = d.kind == P2C_KIND_POSE_CHANGES_6D
+                             ? (def ? train_clip_kernel<P2C_KIND_POSE_CHANGES_6D, CFG_DEFAULT> : train_clip_kernel<P2C_KIND_POSE_CHANGES_6D, CFG_GENERIC>)
+                             : (def ? train_clip_kernel<P2C_KIND_RELATIVE_ROT_6D, CFG_DEFAULT> : train_clip_kernel<P2C_KIND_RELATIVE_ROT_6D, CFG_GENERIC>);
+    hipLaunchKernelGGL(kernel, grid_a, dim3(64 * WAVES), lds_a, stream, d, gl, ca);
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
   }
