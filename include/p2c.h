@@ -1060,6 +1060,50 @@ typedef struct p2c_clip_frames_desc {
 P2C_API int64_t p2c_clip_frames_workspace_bytes(int64_t frames);
 P2C_API int p2c_clip_frames_fwd(const p2c_clip_frames_desc *desc, void *stream);
 
+/* ---- K34: skeleton clips -> the video logger's uint8 frames (csrc/p2c_render.hip) ---------------------------------------------
+ * What the reference's PedestrianWriter does on the host per frame and panel (a PIL canvas, one ellipse per joint, panels
+ * concatenated with numpy), for every panel, video and frame in ONE launch with no memset in front of it.
+ *   out      uint8 (V, T, rows H, cols W, 3); cell k = panel k sits at rows (k / cols) H.., columns (k % cols) W..; a panel whose
+ *            points are NULL and the cells from n_panels on are zero. Every byte is written exactly once.
+ *   panel    points fp32 (V, T, J, C >= 2), columns 0 / 1 = x (column) / y (row), further columns ignored; colors uint8 (J, 3);
+ *            edges int32 (E, 2) joint indices (an index outside [0, J) draws nothing), NULL when E == 0.
+ * All arithmetic behind the rounding is integer. Centre c = rint(x, y) (fp32, half to even); a joint is valid when both
+ * coordinates are finite and |c| <= 16383; an invalid joint and its bones draw nothing. Background 0. Bones first, in edge order,
+ * only when line_width = L > 0: bone (a, b), d = c_b - c_a, q = p - c_a, s = q.d, n = d.d (int64): s <= 0: 4 |q|^2 <= L^2;
+ * s >= n: 4 |p - c_b|^2 <= L^2; else 4 (q x d)^2 <= L^2 n; colour colors[b]. Then joints in index order: |p - c_j|^2 <= radius^2,
+ * colour colors[j]. A later primitive overwrites an earlier one.
+ * A workgroup owns a 16 x 64 pixel tile of one (cell, video, frame): it rounds the frame's centres, compacts into LDS, in draw
+ * order, the primitives whose bounding box grown by radius / ceil(L / 2) meets the tile, and each lane decides four pixels of a
+ * row and stores their 12 bytes. Workgroups stride over the tiles; max_blocks 0: the kernel's own grid cap, > 0 lowers it.
+ * p2c_render_points_supported: 0 <= n_panels <= min(P2C_RENDER_MAX_PANELS, rows cols), 0 <= J, E <= P2C_RENDER_MAX_PRIMS per panel,
+ * C >= 2, 1 <= H, W <= 8192, W % 4 == 0, 0 <= radius, line_width <= P2C_RENDER_MAX_REACH, V, T, rows, cols >= 1.
+ * p2c_render_points_fwd: P2C_E_SHAPE for what _supported refuses and for max_blocks < 0; P2C_E_NULL for a missing out, a panel
+ * with points but no colors, or E > 0 without edges; both before any launch. No workspace, no host sync: capturable. */
+#define P2C_RENDER_MAX_PANELS 8
+#define P2C_RENDER_MAX_PRIMS 64
+#define P2C_RENDER_MAX_REACH 64
+#define P2C_RENDER_MAX_SIDE 8192
+#define P2C_RENDER_MAX_COORD 16383
+typedef struct p2c_render_panel {
+  const float *points;
+  const uint8_t *colors;
+  const int32_t *edges;
+  int32_t J, E, C;
+  int32_t reserved;
+} p2c_render_panel;
+typedef struct p2c_render_points_desc {
+  int32_t V, T;
+  int32_t H, W;
+  int32_t rows, cols;
+  int32_t n_panels;
+  int32_t radius, line_width;
+  int32_t max_blocks;
+  uint8_t *out;
+  p2c_render_panel panels[P2C_RENDER_MAX_PANELS];
+} p2c_render_points_desc;
+P2C_API int p2c_render_points_supported(const p2c_render_points_desc *desc);   /* 1 = the shapes the kernel covers */
+P2C_API int p2c_render_points_fwd(const p2c_render_points_desc *desc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -233,6 +233,21 @@ class ClipFramesDesc(ctypes.Structure):
                 ('clips', ClipFramesClip * P2C_FRAMES_MAX_CLIPS)]
 
 
+P2C_RENDER_MAX_PANELS, P2C_RENDER_MAX_PRIMS, P2C_RENDER_MAX_REACH, P2C_RENDER_MAX_SIDE, P2C_RENDER_MAX_COORD = 8, 64, 64, 8192, 16383
+
+
+class RenderPanel(ctypes.Structure):
+    """p2c_render_panel (include/p2c.h)."""
+    _fields_ = [('points', _f32p), ('colors', _vp), ('edges', _vp), ('J', _i32), ('E', _i32), ('C', _i32), ('reserved', _i32)]
+
+
+class RenderPointsDesc(ctypes.Structure):
+    """p2c_render_points_desc (include/p2c.h)."""
+    _fields_ = [('V', _i32), ('T', _i32), ('H', _i32), ('W', _i32), ('rows', _i32), ('cols', _i32), ('n_panels', _i32),
+                ('radius', _i32), ('line_width', _i32), ('max_blocks', _i32), ('out', _vp),
+                ('panels', RenderPanel * P2C_RENDER_MAX_PANELS)]
+
+
 SYMBOLS = {
     'p2c_version': (ctypes.c_char_p, []),
     'p2c_pose_head_workspace_floats': (_i64, [_i32]),
@@ -348,6 +363,8 @@ SYMBOLS = {
     'p2c_lift_fwd': (ctypes.c_int, [ctypes.POINTER(LiftDesc), _vp]),
     'p2c_clip_frames_workspace_bytes': (_i64, [_i64]),
     'p2c_clip_frames_fwd': (ctypes.c_int, [ctypes.POINTER(ClipFramesDesc), _vp]),
+    'p2c_render_points_supported': (ctypes.c_int, [ctypes.POINTER(RenderPointsDesc)]),
+    'p2c_render_points_fwd': (ctypes.c_int, [ctypes.POINTER(RenderPointsDesc), _vp]),
 }
 
 _lib = None

@@ -11,8 +11,8 @@ Differences, all about host synchronisation:
     Here a NaN/inf loss is dropped only when ``strict_nan_check=True`` (reference behaviour, syncs); by default the value
     is kept on device and ``check_finite()`` can be called every N steps.
   * ``self.log`` receives device tensors; nothing calls ``.item()`` inside the step.
-Video logging / W&B are out of scope; validation metrics are device metrics (``get_metrics``) and
-``_log_videos`` is a no-op hook.
+W&B is out of scope; validation metrics are device metrics (``get_metrics``). ``_log_videos`` forwards the
+validation / test tensors to the trainer's ``PedestrianLogger`` (loggers/pedestrian) and does nothing without one.
 """
 import platform
 from types import FunctionType
@@ -253,5 +253,20 @@ class LitBaseFlow(LightningModuleBase):
         if bad:
             raise RuntimeError("Couldn't calculate any loss. Non-finite: {}".format(bad))
 
-    def _log_videos(self, **kwargs):
-        pass    # PedestrianLogger is out of scope; benchmarks run with --renderers none
+    def _log_videos(self, meta=None, batch_idx=0, stage='train', **sliced):
+        """Validation and test steps hand their (already materialised) tensors to every ``PedestrianLogger`` of the trainer; the
+        writer's interval gate decides. Stage ``train`` stays a no-op here: the lean train step returns no projection and a
+        replayed graph runs no Python -- ``Trainer.fit`` logs training clips from one extra eval-mode forward instead."""
+        if stage not in ('val', 'test'):
+            return
+        trainer = getattr(self, 'trainer', None)
+        loggers = getattr(trainer, 'loggers', None)
+        if not loggers:
+            return
+        from pedestrians_video_2_carla_amd.loggers.pedestrian import PedestrianLogger
+        for logger in loggers:
+            if isinstance(logger, PedestrianLogger):
+                logger.experiment.log_videos(meta=meta, step=trainer.global_step, batch_idx=batch_idx, stage=stage,
+                                             inputs=sliced.get('inputs'), targets=sliced.get('targets'),
+                                             projection_2d=sliced.get('projection_2d'),
+                                             projection_2d_transformed=sliced.get('projection_2d_transformed'))

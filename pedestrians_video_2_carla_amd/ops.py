@@ -3669,3 +3669,172 @@ def clip_frames(clips, target_size: int, centres=None, canvas=None) -> Tensor:
                 clip.canvas = 0 if canvas is None else int(canvas[i0 + k])
             _lib.check(lib.p2c_clip_frames_fwd(ctypes.byref(d), _stream()), 'p2c_clip_frames_fwd')
     return out
+
+
+# ---- K34: skeleton clips -> the video logger's uint8 frames (csrc/p2c_render.hip) ---------------------------------------------
+RENDER_MAX_COORD = _lib.P2C_RENDER_MAX_COORD
+_RENDER_CHUNK = 1 << 23               # elements of one (frames, primitives, H, W) mask block of the tensor definition
+
+
+def render_framework() -> bool:
+    """P2C_RENDER_FRAMEWORK=1: ``render_points`` runs its tensor definition on the points' device (the comparison arm of
+    tools/bench_render.py)."""
+    return os.environ.get('P2C_RENDER_FRAMEWORK', '0') == '1'
+
+
+def _render_panels(panels):
+    """Checked panels: None or (points (V,T,J,C>=2) float, colors (J,3) uint8, edges (E,2) int64), all on the points' device."""
+    out, lead = [], None
+    for k, panel in enumerate(panels):
+        if panel is None:
+            out.append(None)
+            continue
+        points, colors, edges = panel
+        if not (isinstance(points, Tensor) and points.ndim == 4 and points.shape[-1] >= 2 and points.is_floating_point()):
+            raise RuntimeError(f'render_points: panel {k}: points are float (V,T,J,C>=2), got {getattr(points, "shape", None)}')
+        J, dev = points.shape[2], points.device
+        if lead is None:
+            lead = points
+        elif tuple(points.shape[:2]) != tuple(lead.shape[:2]) or dev != lead.device:
+            raise RuntimeError(f'render_points: panel {k} has (V,T) {tuple(points.shape[:2])} on {dev}; '
+                               f'{tuple(lead.shape[:2])} on {lead.device} expected')
+        colors = torch.as_tensor(colors)
+        if tuple(colors.shape) != (J, 3) or colors.dtype != torch.uint8:
+            raise RuntimeError(f'render_points: panel {k}: colors are uint8 ({J},3), got {colors.dtype} {tuple(colors.shape)}')
+        edges = torch.as_tensor(edges if edges is not None else [], dtype=torch.int64).reshape(-1, 2)
+        if edges.numel() and bool(((edges < 0) | (edges >= J)).any()):
+            raise RuntimeError(f'render_points: panel {k}: an edge names a joint outside [0, {J})')
+        out.append((points.detach(), colors.to(dev), edges.to(dev)))
+    if lead is None:
+        raise RuntimeError('render_points: at least one panel needs points (they carry V and T)')
+    return out, lead
+
+
+def _render_last_cover(best: Tensor, mask: Tensor, first: int) -> None:
+    """best (n,H,W) <- max(best, index + 1 of the last primitive of ``mask`` (n,P,H,W) that covers the pixel), indices from ``first``."""
+    index = torch.arange(first + 1, first + 1 + mask.shape[1], device=mask.device).view(1, -1, 1, 1)
+    torch.maximum(best, (index * mask).amax(1), out=best)
+
+
+def _render_panel_tensor(points: Tensor, colors: Tensor, edges: Tensor, H: int, W: int, radius: int, line_width: int) -> Tensor:
+    """One panel, (V,T,H,W,3) uint8: masks over (frames, primitive, H, W) -- bones in edge order, then joints in index order -- the
+    last covering primitive by ``amax`` of (index + 1) * mask, then the colour gathered. int64 throughout (include/p2c.h, K34)."""
+    V, T, J = points.shape[:3]
+    dev, N = points.device, V * T
+    xy = torch.round(points[..., :2].to(torch.float32)).reshape(N, J, 2)
+    valid = (torch.isfinite(xy) & (xy.abs() <= RENDER_MAX_COORD)).all(-1)                       # (N,J)
+    c = torch.where(valid[..., None], xy, torch.zeros_like(xy)).to(torch.int64)
+    E = edges.shape[0] if line_width > 0 else 0
+    table = torch.cat([colors.new_zeros(1, 3), colors[edges[:E, 1]], colors])                   # 0: background
+    px = torch.arange(W, device=dev, dtype=torch.int64).view(1, 1, 1, W)
+    py = torch.arange(H, device=dev, dtype=torch.int64).view(1, 1, H, 1)
+    out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=dev)
+    L2, r2 = int(line_width) ** 2, int(radius) ** 2
+    per = max(1, _RENDER_CHUNK // (H * W))                   # (frame, primitive) pairs per block
+    n_step = max(1, per // max(1, max(E, J)))
+    p_step = max(1, per // n_step)
+    for n0 in range(0, N, n_step):
+        cn, vn = c[n0:n0 + n_step], valid[n0:n0 + n_step]
+        best = torch.zeros(cn.shape[0], H, W, dtype=torch.int64, device=dev)
+        for e0 in range(0, E, p_step):
+            a, b = edges[e0:e0 + p_step, 0], edges[e0:e0 + p_step, 1]
+            ca, cb = cn[:, a], cn[:, b]                                                          # (n,P,2)
+            ok = (vn[:, a] & vn[:, b])[..., None, None]
+            ax, ay, bx, by = (t[..., None, None] for t in (ca[..., 0], ca[..., 1], cb[..., 0], cb[..., 1]))
+            dx, dy, qx, qy = bx - ax, by - ay, px - ax, py - ay
+            s, n = qx * dx + qy * dy, dx * dx + dy * dy
+            near_a = 4 * (qx * qx + qy * qy) <= L2
+            near_b = 4 * ((px - bx) ** 2 + (py - by) ** 2) <= L2
+            cross = qx * dy - qy * dx
+            between = 4 * cross * cross <= L2 * n
+            mask = torch.where(s <= 0, near_a, torch.where(s >= n, near_b, between)) & ok
+            _render_last_cover(best, mask, e0)
+        for j0 in range(0, J, p_step):
+            cj = cn[:, j0:j0 + p_step]
+            ex, ey = px - cj[..., 0, None, None], py - cj[..., 1, None, None]
+            mask = (ex * ex + ey * ey <= r2) & vn[:, j0:j0 + p_step, None, None]
+            _render_last_cover(best, mask, E + j0)
+        out[n0:n0 + n_step] = table[best]
+    return out.view(V, T, H, W, 3)
+
+
+def _render_points_tensor(panels, size, layout, radius: int = 2, line_width: int = 0) -> Tensor:
+    """The definition of ``render_points`` on tensor ops (and its fallback): checked ``panels`` as ``_render_panels`` returns them."""
+    (H, W), (rows, cols) = size, layout
+    lead = next(p[0] for p in panels if p is not None)
+    V, T = lead.shape[:2]
+    out = torch.zeros(V, T, rows * H, cols * W, 3, dtype=torch.uint8, device=lead.device)
+    for k, panel in enumerate(panels):
+        if panel is not None:
+            r, c = divmod(k, cols)
+            out[:, :, r * H:(r + 1) * H, c * W:(c + 1) * W] = _render_panel_tensor(*panel, H, W, radius, line_width)
+    return out
+
+
+def _render_desc(panels, V, T, H, W, rows, cols, radius, line_width, max_blocks=0):
+    """``p2c_render_points_desc`` without pointers: the shapes ``p2c_render_points_supported`` judges. More panels than the
+    descriptor holds are counted, not described."""
+    d = _lib.RenderPointsDesc()
+    d.V, d.T, d.H, d.W, d.rows, d.cols, d.n_panels = V, T, H, W, rows, cols, len(panels)
+    d.radius, d.line_width, d.max_blocks = int(radius), int(line_width), int(max_blocks)
+    for k, panel in enumerate(panels[:_lib.P2C_RENDER_MAX_PANELS]):
+        if panel is not None:
+            points, _colors, edges = panel
+            d.panels[k].J, d.panels[k].E, d.panels[k].C = points.shape[2], edges.shape[0], points.shape[3]
+    return d
+
+
+def render_points_supported(panels, size, layout, radius: int = 2, line_width: int = 0) -> bool:
+    """What K34 covers, asked of the library (``p2c_render_points_supported``): at most 8 panels, J and E up to 64 per panel, H and W
+    up to 8192 with W a multiple of 4, radius and line width up to 64 -- for fp32 points on the device and without
+    ``P2C_RENDER_FRAMEWORK=1``."""
+    return _render_supported(*_render_panels(panels), size, layout, radius, line_width)
+
+
+def _render_supported(checked, lead, size, layout, radius, line_width) -> bool:
+    if render_framework() or not all(p is None or (p[0].is_cuda and p[0].dtype == torch.float32) for p in checked):
+        return False
+    d = _render_desc(checked, lead.shape[0], lead.shape[1], int(size[0]), int(size[1]), int(layout[0]), int(layout[1]), radius, line_width)
+    for k, panel in enumerate(checked[:_lib.P2C_RENDER_MAX_PANELS]):
+        if panel is not None:
+            d.panels[k].points = 1        # "this panel draws": the answer does not read through the pointer
+    return bool(_lib.lib().p2c_render_points_supported(ctypes.byref(d)))
+
+
+def render_points(panels, size=(800, 600), layout=(1, 1), radius: int = 2, line_width: int = 0, max_blocks: int = 0) -> Tensor:
+    """Skeleton clips -> merged uint8 frames (V, T, rows*H, cols*W, 3), the video logger's pixels. ``panels``: a sequence of None
+    or ``(points (V,T,J,C>=2) float, colors (J,3) uint8, edges (E,2) joint indices)``; panel k fills cell (k // cols, k % cols) of
+    ``layout = (rows, cols)``, each cell ``size = (H, W)``; None panels and unused cells are zero. Rules (include/p2c.h, K34): centre
+    = rint(x, y) in fp32, x the column; non-finite or |c| > 16383 draws nothing; bones (only with ``line_width`` > 0) in edge order
+    in the colour of their second joint, then joints as discs of ``radius`` in index order, later over earlier.
+    fp32 device points inside ``render_points_supported`` take K34: ONE launch for every panel, video and frame, no memset. Host
+    tensors, other float types, refused shapes and ``P2C_RENDER_FRAMEWORK=1`` take the tensor definition, which gives the same
+    bytes. ``max_blocks`` lowers the grid cap (tests)."""
+    (H, W), (rows, cols) = (int(v) for v in size), (int(v) for v in layout)
+    radius, line_width = int(radius), int(line_width)
+    if H < 1 or W < 1 or rows < 1 or cols < 1 or radius < 0 or line_width < 0:
+        raise RuntimeError(f'render_points: size {size}, layout {layout}, radius {radius}, line_width {line_width}')
+    checked, lead = _render_panels(panels)
+    if len(checked) > rows * cols:
+        raise RuntimeError(f'render_points: {len(checked)} panels for a layout of {rows} x {cols} cells')
+    V, T = lead.shape[:2]
+    if V == 0 or T == 0:
+        return torch.zeros(V, T, rows * H, cols * W, 3, dtype=torch.uint8, device=lead.device)
+    if not _render_supported(checked, lead, (H, W), (rows, cols), radius, line_width):
+        return _render_points_tensor(checked, (H, W), (rows, cols), radius, line_width)
+    dev = lead.device
+    keep = []               # contiguous operands stay alive until the launch is issued
+    d = _render_desc(checked, V, T, H, W, rows, cols, radius, line_width, max_blocks)
+    for k, panel in enumerate(checked):
+        if panel is None or panel[0].shape[2] == 0:
+            continue
+        points, colors, edges = panel
+        points, colors, edges = points.contiguous(), colors.contiguous(), edges.to(torch.int32).contiguous()
+        keep += [points, colors, edges]
+        d.panels[k].points, d.panels[k].colors = points.data_ptr(), colors.data_ptr()
+        d.panels[k].edges = edges.data_ptr() if edges.numel() else None
+    out = torch.empty(V, T, rows * H, cols * W, 3, dtype=torch.uint8, device=dev)
+    d.out = out.data_ptr()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().p2c_render_points_fwd(ctypes.byref(d), _stream()), 'p2c_render_points_fwd')
+    return out

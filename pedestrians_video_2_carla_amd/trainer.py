@@ -68,7 +68,8 @@ def ranks_agree(ok: bool, device, checksum: Optional[torch.Tensor] = None, group
 class Trainer:
     def __init__(self, max_steps: int = 100, use_graph: bool = False, device: Optional[torch.device] = None,
                  flatten: bool = True, log_every_n_steps: int = 0, steps_per_epoch: Optional[int] = None,
-                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = 'norm'):
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = 'norm',
+                 loggers: Optional[Iterable] = None):
         # Lightning's names and defaults (the reference's trainer takes them from argparse, modeling.py:275, 353): None / 0 = off
         if gradient_clip_algorithm not in ('norm', 'value'):
             raise ValueError(f"gradient_clip_algorithm must be 'norm' or 'value', not {gradient_clip_algorithm!r}")
@@ -85,7 +86,7 @@ class Trainer:
         self.log_every_n_steps = log_every_n_steps
         self.steps_per_epoch = steps_per_epoch
         self.datamodule = None
-        self.loggers: List = []
+        self.loggers: List = list(loggers) if loggers is not None else []       # a PedestrianLogger in here writes clips
         self.global_step = 0
         self.current_epoch = 0
         self.flat: Optional[FlatParameters] = None
@@ -711,6 +712,40 @@ class Trainer:
             flow.train(was_training)
             lifter.close()
 
+    def _video_writers(self) -> List:
+        """The writers of the attached ``PedestrianLogger``s that write at all (none attached: the loggers module is not imported)."""
+        if not self.loggers:
+            return []
+        from pedestrians_video_2_carla_amd.loggers.pedestrian import PedestrianLogger
+        return [lg.experiment for lg in self.loggers if isinstance(lg, PedestrianLogger) and not lg.disabled]
+
+    def _log_train_videos(self, flow, batch, step: int, writers: List) -> None:
+        """Training clips. The reference logs the train-mode outputs of the step itself; here the lean train step returns no
+        projection and a replayed graph runs no Python, so after a step whose index passes a writer's gate the batch goes through
+        ONE extra forward (``flow.predict_step``: eval mode, no gradients -- no dropout stream and no BatchNorm statistic moves),
+        logged as stage ``train``. The flow's mode and per-batch state are put back: the training steps are what they are without a
+        logger."""
+        writers = [w for w in writers if w.wants(step)]
+        if not writers:
+            return
+        was_training = flow.training
+        projection = getattr(flow, 'projection', None)
+        held = {o: {k: getattr(o, k) for k in keys if hasattr(o, k)}
+                for o, keys in ((flow, ('_pair_counts',)), (projection, ('_skel_type', '_batch_size'))) if o is not None}
+        flow.eval()
+        try:
+            with torch.no_grad():
+                sliced, meta = flow.predict_step(batch, step)
+                for w in writers:
+                    w.log_videos(meta=meta, step=step, batch_idx=step, stage='train', inputs=sliced.get('inputs'),
+                                 targets=sliced.get('targets'), projection_2d=sliced.get('projection_2d'),
+                                 projection_2d_transformed=sliced.get('projection_2d_transformed'))
+        finally:
+            flow.train(was_training)
+            for o, values in held.items():
+                for k, v in values.items():
+                    setattr(o, k, v)
+
     def fit(self, flow, datamodule, batches: Optional[Iterable] = None):
         self.setup(flow, datamodule)
         device = self.device or flow.device
@@ -718,10 +753,13 @@ class Trainer:
             rank = dist.get_rank() if dist.is_initialized() else 0
             batches = datamodule.train_batches(device, self.max_steps, rank=rank)
         losses = []
+        writers = self._video_writers()
         for i, batch in enumerate(batches):
             if i >= self.max_steps:
                 break
             losses.append(self.train_step(flow, batch, i))
+            if writers:
+                self._log_train_videos(flow, batch, i, writers)
             if self.log_every_n_steps and (i + 1) % self.log_every_n_steps == 0:
                 flow.check_finite('train')
             if self.steps_per_epoch and (i + 1) % self.steps_per_epoch == 0:
