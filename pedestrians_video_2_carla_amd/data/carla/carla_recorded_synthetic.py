@@ -75,6 +75,27 @@ class SyntheticCarlaRecordedDataModule(BaseDataModule):
         }
         return frames, targets, meta
 
-    def train_batches(self, device, steps: int, rank: int = 0):
-        for i in range(steps):
+    def train_batches(self, device, steps: int, rank: int = 0, first_step: int = 0):
+        """``first_step``: a resumed run draws the batches the uninterrupted one would (step i is seeded by i alone)."""
+        for i in range(first_step, first_step + steps):
             yield self.generate_batch(device, seed_offset=rank + 1000 * i)
+
+    # Validation / test sets: fixed, generated once per device and kept. Their seed offsets are negative; every training step's is
+    # rank + 1000 i >= 0, so no training batch is ever one of them. The last batch is half a batch: an epoch mean weighted by
+    # batch size differs from the plain mean of the batch values.
+    _EVAL_SEED_OFFSETS = {'val': -1_000_000, 'test': -2_000_000}
+
+    def _eval_batches(self, device, stage: str, n_batches: int) -> List[Batch]:
+        cache = self.__dict__.setdefault('_eval_cache', {})
+        key = (stage, str(device), n_batches)
+        if key not in cache:
+            sizes = [self.batch_size] * (n_batches - 1) + [max(self.batch_size // 2, 1)]
+            cache[key] = [self.generate_batch(device, batch_size=b, seed_offset=self._EVAL_SEED_OFFSETS[stage] - i)
+                          for i, b in enumerate(sizes)]
+        return cache[key]
+
+    def val_batches(self, device, n_batches: int = 2) -> List[Batch]:
+        return self._eval_batches(device, 'val', n_batches)
+
+    def test_batches(self, device, n_batches: int = 2) -> List[Batch]:
+        return self._eval_batches(device, 'test', n_batches)

@@ -101,6 +101,13 @@ class LitBaseFlow(LightningModuleBase):
     def get_default_models(cls) -> Dict[str, torch.nn.Module]:
         return {}
 
+    @classmethod
+    def load_from_checkpoint(cls, checkpoint_path: str, map_location=None, **kwargs):
+        """Lightning's ``load_from_checkpoint``: the flow of the file's ``hyper_parameters`` (keyword arguments win) with its
+        ``state_dict`` loaded; see ``checkpoint.load_from_checkpoint``."""
+        from pedestrians_video_2_carla_amd import checkpoint
+        return checkpoint.load_from_checkpoint(cls, checkpoint_path, map_location=map_location, **kwargs)
+
     def get_metrics(self):
         """Metrics updated on every validation / test batch (reference base.py:146-151). The flows return device metrics
         (``pedestrians_video_2_carla_amd.metrics``): one HIP launch per update, host sync only in ``compute()``."""

@@ -14,10 +14,16 @@ Two execution modes:
 ``gradient_clip_val`` / ``gradient_clip_algorithm`` are Lightning's arguments of the same names: the clip runs inside FlatAdamW's
 launches (K29, csrc/p2c_grad_clip.hip) -- after the all-reduce, so the averaged gradient is what is clipped -- or through
 torch.nn.utils.clip_grad_* for any other optimizer; with a clip the optimizer is never fused into a backward.
+``max_epochs`` / ``check_val_every_n_epoch`` / ``callbacks`` and ``fit(..., val_batches=, ckpt_path=)`` turn ``fit`` into the epoch
+loop (``_fit_epochs``: validation -> epoch-interval LR schedulers -> callbacks at the end of every epoch); ``save_checkpoint`` /
+``load_checkpoint`` (checkpoint.py) carry everything a resumed run needs to be the uninterrupted one, bit for bit. None of it
+runs per step: the step's launches are the same with and without it.
 """
 import contextlib
+import gc
 import os
 import sys
+import weakref
 from typing import Dict, Iterable, List, Optional
 
 import torch
@@ -66,10 +72,25 @@ def ranks_agree(ok: bool, device, checksum: Optional[torch.Tensor] = None, group
 
 
 class Trainer:
-    def __init__(self, max_steps: int = 100, use_graph: bool = False, device: Optional[torch.device] = None,
+    def __init__(self, max_steps: Optional[int] = None, use_graph: bool = False, device: Optional[torch.device] = None,
                  flatten: bool = True, log_every_n_steps: int = 0, steps_per_epoch: Optional[int] = None,
                  gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = 'norm',
-                 loggers: Optional[Iterable] = None):
+                 loggers: Optional[Iterable] = None, max_epochs: Optional[int] = None, check_val_every_n_epoch: int = 1,
+                 callbacks: Optional[Iterable] = None):
+        # ``max_steps``: 100 when neither it nor ``max_epochs`` is given; with ``max_epochs`` alone the epochs bound the run, with
+        # both whichever comes first (Lightning's rule)
+        if max_steps is None and max_epochs is None:
+            max_steps = 100
+        if check_val_every_n_epoch < 1:
+            raise ValueError(f'check_val_every_n_epoch must be at least 1, not {check_val_every_n_epoch!r}')
+        self.max_epochs = max_epochs
+        self.check_val_every_n_epoch = int(check_val_every_n_epoch)
+        self.callbacks: List = list(callbacks) if callbacks is not None else []
+        self.callback_metrics: Dict[str, float] = {}      # the monitors of the last validation / test epoch
+        self._ref_params: List[torch.nn.Parameter] = []   # the parameters in the order the plugin gave them to its optimizer
+        self._flow_ref = None                             # weak: flow.trainer points here, a cycle would leave GPU objects to the GC
+        self._train_batches = None
+        self._rng_after_capture = None                    # set by a full checkpoint load (checkpoint.load)
         # Lightning's names and defaults (the reference's trainer takes them from argparse, modeling.py:275, 353): None / 0 = off
         if gradient_clip_algorithm not in ('norm', 'value'):
             raise ValueError(f"gradient_clip_algorithm must be 'norm' or 'value', not {gradient_clip_algorithm!r}")
@@ -108,10 +129,18 @@ class Trainer:
         self._graph_nodes = None
         self._handed_over = None
 
+    @property
+    def _flow(self):
+        """The flow of the last ``setup`` (held weakly: ``flow.trainer`` is the strong direction. A trainer in a reference cycle is
+        destroyed by the cyclic collector at a time of its choosing, and releasing captured graphs, events or pinned buffers while
+        ANOTHER trainer's stream capture is open aborts the process)."""
+        return self._flow_ref() if self._flow_ref is not None else None
+
     # ------------------------------------------------------------------------------------------------------------
     def setup(self, flow, datamodule):
         self.datamodule = datamodule
         flow.trainer = self
+        self._flow_ref = weakref.ref(flow)
         if self.device is not None:
             flow.to(self.device)
         flow.train()
@@ -132,6 +161,7 @@ class Trainer:
                 self._grad_sinks = True          # K12 adds weight gradients straight into the flat gradient buffer's views
             if len(configs) != 1:
                 raise ValueError('exactly one trainable plugin expected (ZeroTrajectory has no optimizer)')
+            self._ref_params = [p for g in configs[0]['optimizer'].param_groups for p in g['params']]   # (checkpoint layout)
             self.optimizers = [self.flat.rebuild_optimizer(configs[0]['optimizer'], **extra)]
             opt = self.optimizers[0]
             # modules with a re-laid-out copy of their weights (the fused MLP's LDS image) let the optimizer keep it current
@@ -312,7 +342,26 @@ class Trainer:
             if self._direct is None or not self._hand_over(flow, batch):
                 static = self.stage_batch(flow, batch, batch_idx)      # copies only when a NEW batch object arrives
             if self._graphs is None:
-                self._capture(flow, static, batch_idx)
+                # No cyclic collection while a capture is open: an object it finalises there (another trainer's graph, a loader's
+                # pinned buffers and events, in a cycle the user's code made) calls the runtime from inside the capture, which aborts
+                # the process. Collected before, paused during.
+                gc.collect()
+                gc_was_enabled = gc.isenabled()
+                gc.disable()
+                try:
+                    self._capture(flow, static, batch_idx)
+                finally:
+                    if gc_was_enabled:
+                        gc.enable()
+                if self._rng_after_capture is not None:
+                    # resumed from a checkpoint: the warm-up steps of the capture drew from the generators; the first replay
+                    # must start where the uninterrupted run's next step did
+                    cpu_state, cuda_state = self._rng_after_capture
+                    self._rng_after_capture = None
+                    if cpu_state is not None:
+                        torch.set_rng_state(cpu_state)
+                    if cuda_state is not None:
+                        torch.cuda.set_rng_state(cuda_state, static[0].device)
                 if not self.use_graph:              # the captured step failed its replay check: eager steps from here on
                     return self.train_step(flow, batch, batch_idx)
             g_fb, g_opt = self._graphs
@@ -669,10 +718,16 @@ class Trainer:
             m.repack()
         torch.cuda.synchronize()
 
-    def validate(self, flow, batches: Iterable) -> Dict[str, float]:
+    def validate(self, flow, batches: Iterable, losses: bool = False) -> Dict[str, float]:
         """One validation epoch over ``batches`` (Lightning's hook order: ``on_validation_batch_start`` -> ``validation_step``),
         in eval mode and without gradients, issued eagerly; the flow's train / eval mode is put back afterwards. Returns the
-        epoch's metrics, all-reduced over the ranks (``flow.compute_metrics(sync=True)``, which also resets them)."""
+        epoch's metrics, all-reduced over the ranks (``flow.compute_metrics(sync=True)``, which also resets them).
+        ``losses=True`` returns the epoch's MONITORS instead: the batch-size-weighted mean of every ``val_loss/*`` value the
+        flow logged (Lightning's ``on_epoch`` reduction, sum(v_b B_b) / sum(B_b)), accumulated on the device and read once, plus
+        the metrics as ``val/<name>`` (the reference's names); the flow's per-batch state is put back as well, so a train step
+        that follows -- captured or not -- is what it would have been without the validation."""
+        if losses:
+            return self._eval_epoch(flow, batches, 'val')
         was_training = flow.training
         flow.eval()
         try:
@@ -683,6 +738,84 @@ class Trainer:
         finally:
             flow.train(was_training)
         return flow.compute_metrics(sync=True)
+
+    def test(self, flow, batches: Iterable, ckpt_path: Optional[str] = None) -> Dict[str, float]:
+        """The same loop with ``on_test_batch_start`` / ``test_step``: ``test_loss/*`` means and ``test/<metric>``. ``ckpt_path``:
+        a checkpoint file, or ``'best'`` for the attached ``ModelCheckpoint``'s ``best_model_path``; its WEIGHTS are loaded
+        (in place: legal on a live, captured trainer), nothing else of it."""
+        if ckpt_path == 'best':
+            ckpt_path = next((cb.best_model_path for cb in self.callbacks if getattr(cb, 'best_model_path', '')), None)
+            if not ckpt_path:
+                raise RuntimeError("test(ckpt_path='best') needs a ModelCheckpoint callback that has saved a checkpoint")
+        if self._flow is None:                     # a trainer that was never set up: the flow still finds its data module
+            flow.trainer = self
+        if ckpt_path is not None:
+            self.load_checkpoint(ckpt_path, weights_only=True, flow=flow)
+        return self._eval_epoch(flow, batches, 'test')
+
+    def _eval_epoch(self, flow, batches: Iterable, stage: str) -> Dict[str, float]:
+        batch_start = flow.on_validation_batch_start if stage == 'val' else flow.on_test_batch_start
+        step = flow.validation_step if stage == 'val' else flow.test_step
+        prefix = f'{stage}_loss/'
+        logged = getattr(flow, 'logged', None)
+        was_training = flow.training
+        projection = getattr(flow, 'projection', None)
+        held = {o: {k: getattr(o, k) for k in keys if hasattr(o, k)}
+                for o, keys in ((flow, ('_pair_counts',)), (projection, ('_skel_type', '_batch_size'))) if o is not None}
+        sums: Dict[str, torch.Tensor] = {}
+        counts: Dict[str, int] = {}
+        flow.eval()
+        try:
+            with torch.no_grad():
+                for i, batch in enumerate(batches):
+                    if logged is not None:             # only what THIS batch logs is folded in
+                        for k in [k for k in logged if k.startswith(prefix)]:
+                            del logged[k]
+                    batch_start(batch, i)
+                    step(batch, i)
+                    n = len(batch[0])
+                    for k, v in (logged or {}).items():
+                        if k.startswith(prefix) and isinstance(v, torch.Tensor) and v.ndim == 0:
+                            term = v.to(torch.float64) * n            # device arithmetic in fp64: nothing is read here
+                            sums[k] = term if k not in sums else sums[k] + term
+                            counts[k] = counts.get(k, 0) + n
+        finally:
+            flow.train(was_training)
+            for o, values in held.items():
+                for k, v in values.items():
+                    setattr(o, k, v)
+        monitors: Dict[str, float] = {}
+        if sums:
+            names = sorted(sums)
+            table = torch.stack([torch.stack([sums[k] for k in names]),
+                                 torch.tensor([float(counts[k]) for k in names], dtype=torch.float64).to(sums[names[0]].device)])
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                dist.all_reduce(table, op=dist.ReduceOp.SUM)
+            monitors.update(zip(names, (table[0] / table[1]).tolist()))       # the epoch's one read of the losses
+        monitors.update({f'{stage}/{k}': v for k, v in flow.compute_metrics(sync=True).items()})
+        self.callback_metrics = {**self.callback_metrics, **monitors}
+        return monitors
+
+    # ---- checkpoints (checkpoint.py) ----------------------------------------------------------------------------------------
+    def save_checkpoint(self, path: str, flow=None) -> str:
+        """Everything a resumed run needs, in one file with Lightning's top-level keys (see checkpoint.py). Rank 0 writes, all
+        ranks wait. Checkpoints written by ``ModelCheckpoint`` sit on epoch boundaries; one made by hand in the middle of an
+        epoch resumes at the NEXT boundary's batch order (mid-epoch data resume is out of scope)."""
+        from pedestrians_video_2_carla_amd import checkpoint
+        return checkpoint.save(self, flow if flow is not None else self._flow, path)
+
+    def load_checkpoint(self, path: str, weights_only: bool = False, flow=None) -> dict:
+        """Full load (weights, optimizer, schedulers, callbacks, counters, dropout streams, generators): only on a trainer that
+        was set up and has not stepped -- anything else raises, nothing is half-restored. ``weights_only=True``: parameters and
+        buffers in place plus re-packed weight images, legal at any time."""
+        from pedestrians_video_2_carla_amd import checkpoint
+        flow = flow if flow is not None else self._flow
+        if flow is None:
+            raise RuntimeError('load_checkpoint needs the flow: call setup() first or pass flow=')
+        ckpt = checkpoint.load(self, flow, path, weights_only=weights_only)
+        if not weights_only:
+            self._loaded_p2c = ckpt.get(checkpoint.P2C_KEY) or {}
+        return ckpt
 
     def predict(self, flow, batches: Iterable) -> List:
         """Lightning's predict loop over ``batches``: ``flow.predict_step(batch, i)`` (which runs the batch-start hook itself) in
@@ -746,9 +879,16 @@ class Trainer:
                 for k, v in values.items():
                     setattr(o, k, v)
 
-    def fit(self, flow, datamodule, batches: Optional[Iterable] = None):
+    def fit(self, flow, datamodule, batches: Optional[Iterable] = None, val_batches=None, ckpt_path: Optional[str] = None):
+        """``max_steps`` steps over ``batches`` (or the data module's), as before -- or, with any of ``max_epochs``,
+        ``val_batches``, ``callbacks``, ``ckpt_path`` given (or ``steps_per_epoch`` and a data module with ``val_batches``), the
+        epoch loop (``_fit_epochs``). Returns the per-step losses (device tensors) of this call."""
         self.setup(flow, datamodule)
         device = self.device or flow.device
+        if val_batches is None and hasattr(datamodule, 'val_batches') and (self.steps_per_epoch or self.max_epochs is not None):
+            val_batches = datamodule.val_batches(device)
+        if self.max_epochs is not None or val_batches is not None or self.callbacks or ckpt_path is not None:
+            return self._fit_epochs(flow, datamodule, batches, val_batches, ckpt_path)
         if batches is None:
             rank = dist.get_rank() if dist.is_initialized() else 0
             batches = datamodule.train_batches(device, self.max_steps, rank=rank)
@@ -767,3 +907,79 @@ class Trainer:
                 self.step_lr_schedulers('epoch', {k: float(v) for k, v in getattr(flow, 'logged', {}).items()
                                                   if isinstance(v, (float, int)) or (isinstance(v, torch.Tensor) and v.ndim == 0)})
         return losses
+
+    # ---- the epoch loop ------------------------------------------------------------------------------------------------------
+    def _fit_epochs(self, flow, datamodule, batches, val_batches, ckpt_path) -> List[torch.Tensor]:
+        """Epochs of ``steps_per_epoch`` steps of ``batches`` -- or one pass over a sized re-iterable (a ``DeviceLoader``, a list)
+        per epoch. End of an epoch, in this order: (1) validation, every ``check_val_every_n_epoch`` epochs; (2) the
+        epoch-interval LR schedulers, with this epoch's monitors; (3) the callbacks' ``on_validation_end``. A checkpoint written
+        in (3) therefore holds the scheduler state the next epoch starts from, which is what makes resuming exact.
+        ``ckpt_path``: full load right after ``setup`` (the trainer has not stepped), then training goes on from the stored
+        epoch and step."""
+        device = self.device or flow.device
+        sized = batches is not None and hasattr(batches, '__len__') and not hasattr(batches, '__next__')
+        self._train_batches = batches if sized else None
+        if ckpt_path is not None:
+            self.load_checkpoint(ckpt_path, flow=flow)
+            epoch = getattr(self, '_loaded_p2c', {}).get('loader_epoch')
+            if sized and epoch is not None and hasattr(batches, 'epoch'):
+                batches.epoch = epoch              # the loader's shuffle order is a function of it
+        if not sized and not self.steps_per_epoch:
+            raise ValueError('the epoch loop needs steps_per_epoch, or batches with a length that can be iterated once per epoch')
+        per_epoch = min(len(batches), self.steps_per_epoch or len(batches)) if sized else self.steps_per_epoch
+        limits = [n for n in (self.max_steps, self.max_epochs * per_epoch if self.max_epochs is not None else None)
+                  if n is not None and n >= 0]
+        if not limits:
+            raise ValueError('the epoch loop needs max_epochs or max_steps')
+        total = min(limits)
+        stream = None
+        if not sized:
+            if batches is None:
+                rank = dist.get_rank() if dist.is_initialized() else 0
+                batches = datamodule.train_batches(device, max(total - self.global_step, 0), rank=rank, first_step=self.global_step)
+            stream = iter(batches)
+        losses: List[torch.Tensor] = []
+        writers = self._video_writers()
+        # a checkpoint made by hand inside an epoch: the rest of that epoch first, so the next boundary is where it would have been
+        carry = min(max(self.global_step - self.current_epoch * per_epoch, 0), per_epoch - 1)
+        while self.global_step < total:
+            source = iter(batches) if sized else stream
+            done, carry = carry, 0
+            for batch in source:
+                i = self.global_step
+                losses.append(self.train_step(flow, batch, i))
+                if writers:
+                    self._log_train_videos(flow, batch, i, writers)
+                if self.log_every_n_steps and (i + 1) % self.log_every_n_steps == 0:
+                    flow.check_finite('train')
+                done += 1
+                if done >= per_epoch or self.global_step >= total:
+                    break
+            if done < per_epoch:
+                if done == 0 or self.global_step >= total or not sized:
+                    break                          # out of batches, or max_steps ended the run inside an epoch: no epoch end
+            self._end_epoch(flow, val_batches, device)
+        for cb in self.callbacks:
+            if hasattr(cb, 'on_fit_end'):
+                cb.on_fit_end(self, flow)
+        return losses
+
+    def _end_epoch(self, flow, val_batches, device) -> None:
+        self.current_epoch += 1
+        validated = val_batches is not None and self.current_epoch % self.check_val_every_n_epoch == 0
+        if validated:
+            source = val_batches(device) if callable(val_batches) else val_batches
+            self._eval_epoch(flow, source, 'val')
+        # Lightning hands a plateau scheduler the last value logged under its key: this epoch's validation mean, the last one
+        # in an epoch without validation, or a training value the flow logged (read only when a scheduler asks for it)
+        monitors = dict(self.callback_metrics)
+        for sched in self.lr_schedulers:
+            key = sched.get('monitor')
+            value = getattr(flow, 'logged', {}).get(key) if key is not None and key not in monitors else None
+            if isinstance(value, (float, int)) or (isinstance(value, torch.Tensor) and value.ndim == 0):
+                monitors[key] = float(value)
+        self.step_lr_schedulers('epoch', monitors)
+        if validated:
+            for cb in self.callbacks:
+                if hasattr(cb, 'on_validation_end'):
+                    cb.on_validation_end(self, flow, dict(self.callback_metrics))
