@@ -1104,6 +1104,32 @@ typedef struct p2c_render_points_desc {
 P2C_API int p2c_render_points_supported(const p2c_render_points_desc *desc);   /* 1 = the shapes the kernel covers */
 P2C_API int p2c_render_points_fwd(const p2c_render_points_desc *desc, void *stream);
 
+/* ---- K35: SMPL body poses (AMASS) -> CARLA bone transforms in one launch (csrc/p2c_smpl.hip) ---------------------------------
+ * What the reference does per clip on a DataLoader worker (data/smpl/smpl_dataset.py:103-142, convert_smpl_to_carla), for N = B T
+ * frames, each independent of every other. fp32.
+ *   body_pose (N,66): 22 joints x 3 Euler angles in ORIGINAL SMPL joint order (Pelvis, L_Hip, R_Hip, Spine1, ...).
+ *   skel_type (N / frames_per_type) int32 on the device, rows of the reference tables; frame n has type
+ *     skel_type[n / frames_per_type] (frames_per_type = T for one type per clip, 1 for one per frame). Not read on the host; a
+ *     value outside [0, 4) is clamped in the kernel.
+ *   ref_rel_loc (4,26,3), ref_rel_rot (4,26,3,3), ref_abs_rot (4,26,3,3): the reference tables.
+ *   world_loc (N,3), world_rot (N,3,3): both NULL or both given; read for `root` only.
+ * Per frame: M[s] = Rx Ry Rz of (-p0, p1, p2) of SMPL joint s; C[bone] = M[its joint], C[spine01] = M[Spine3] M[Spine2];
+ * L = ref_abs_rot[t][bone] K, K = [[1,0,0],[0,0,-1],[0,1,0]]; relative_pose_rot = (L^T C L) ref_rel_rot[t][bone], and
+ * ref_rel_rot[t][bone] itself for the five bones without an SMPL joint; absolute_pose_loc / _rot = forward kinematics of
+ * (ref_rel_loc[t], relative_pose_rot) in the row-vector convention; bones = the p2c_carla_pose_fwd row of (ref_rel_loc[t],
+ * relative_pose_rot); root = that of (world_loc, world_rot).
+ * Outputs, each NULL or given, only the given ones are written: relative_pose_rot (N,26,3,3), absolute_pose_loc (N,26,3),
+ * absolute_pose_rot (N,26,3,3), bones (N,26,6), root (N,6). What is written does not depend on which others are asked for.
+ * max_blocks  0: the kernel's own grid cap; > 0 lowers it (groups of 32 lanes stride over the frames).
+ * No masking: a NaN joint gives NaN in its bone and the bone's descendants, nowhere else. One writer per element, nothing reduced:
+ * two runs give the same bits. N = 0: nothing is launched. N < 0, frames_per_type < 1, max_blocks < 0: P2C_E_SHAPE; a missing input,
+ * no output at all, one world input without the other, root without world inputs: P2C_E_NULL; all before any launch. */
+P2C_API int p2c_smpl_to_carla_fwd(const float *body_pose, const int32_t *skel_type, int64_t frames_per_type,
+                                  const float *ref_rel_loc, const float *ref_rel_rot, const float *ref_abs_rot,
+                                  const float *world_loc, const float *world_rot, float *relative_pose_rot,
+                                  float *absolute_pose_loc, float *absolute_pose_rot, float *bones, float *root, int64_t N,
+                                  int32_t max_blocks, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

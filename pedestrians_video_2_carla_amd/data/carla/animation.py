@@ -2,7 +2,9 @@
 
 One ``.npz`` with ``bones`` (N,T,J,6) and ``root`` (N,T,6) -- rows of (x, y, z, pitch, yaw, roll), metres and degrees, CARLA's
 axes, see ``ops.carla_pose_export`` -- ``bone_names`` (J), ``age`` / ``gender`` (N: which walker blueprint a clip belongs to)
-and ``fps``. Playing it needs a CARLA server and is not part of this package.
+and ``fps``. Playing it needs a CARLA server and is not part of this package. Three writers, one file format: predictions
+(``save_carla_animation``), keypoint clips through a LinearAE flow (``lift_carla_animation``, K32) and mocap clips
+(``retarget_carla_animation``, K35).
 """
 from typing import Dict
 
@@ -38,6 +40,26 @@ def lift_carla_animation(path: str, flow, batches, fps: float = 30.0) -> str:
         rows.append((both[..., :-1, :], both[..., -1, :], meta))
     if not rows:
         raise ValueError('no predictions to save')
+    return _write(path, rows, fps)
+
+
+def retarget_carla_animation(path: str, batches, fps: float = 30.0, device=None) -> str:
+    """Mocap clips as the file ``save_carla_animation`` writes: ``batches`` of ``(frames, targets, meta)`` whose targets hold
+    ``amass_body_pose`` (B,T,66) -- the stored AMASS subsets, a mixture's AMASS clips -- and ``world_rot`` (B,T,3,3) where the
+    subset has it (the identity otherwise; the root location of a body pose is zero). One ``ops.smpl_to_carla`` call per batch
+    (K35 on device tensors: one launch) and one copy to the host: bones and root travel together."""
+    import torch
+    from pedestrians_video_2_carla_amd.walker_control.smpl_retargeter import SmplRetargeter
+    retargeter = SmplRetargeter(device)
+    rows = []
+    for _, targets, meta in batches:
+        if 'amass_body_pose' not in targets:
+            raise KeyError('amass_body_pose is missing from the targets: not a batch of AMASS clips')
+        bones, root = retargeter.export(targets['amass_body_pose'], meta, targets.get('world_rot'))
+        both = torch.cat((bones, root.unsqueeze(-2)), -2).cpu().numpy()
+        rows.append((both[..., :-1, :], both[..., -1, :], meta))
+    if not rows:
+        raise ValueError('no clips to save')
     return _write(path, rows, fps)
 
 

@@ -35,6 +35,36 @@ class SMPL_SKELETON(Skeleton):
 
 
 _S = SMPL_SKELETON
+
+# joint order of the original SMPL body model, which AMASS body poses are stored in (reference skeleton.py:9-34)
+ORIGINAL_SMPL_JOINTS = ('Pelvis L_Hip R_Hip Spine1 L_Knee R_Knee Spine2 L_Ankle R_Ankle Spine3 L_Foot R_Foot Neck L_Collar '
+                        'R_Collar Head L_Shoulder R_Shoulder L_Elbow R_Elbow L_Wrist R_Wrist').split()
+FROM_ORIGINAL = tuple(ORIGINAL_SMPL_JOINTS.index(n) for n in _SMPL)       # SMPL_SKELETON joint s <- original joint [s]
+TO_ORIGINAL = tuple(_SMPL.index(n) for n in ORIGINAL_SMPL_JOINTS)
+
+
+def map_from_original(tensor):
+    """(..., 66) or (..., 22, 3) in original SMPL joint order -> (..., 22, 3) in ``SMPL_SKELETON`` order (reference :132-142)."""
+    if tensor.shape[-1] == len(_SMPL) * 3:
+        tensor = tensor.reshape(tuple(tensor.shape[:-1]) + (len(_SMPL), 3))
+    if tuple(tensor.shape[-2:]) != (len(_SMPL), 3):
+        raise ValueError(f'map_from_original: (..., 66) or (..., 22, 3) expected, got {tuple(tensor.shape)}')
+    return tensor[..., FROM_ORIGINAL, :]
+
+
+def map_to_original(tensor, reshape=True):
+    """The inverse: (..., 22, 3) in ``SMPL_SKELETON`` order -> original order, flattened to (..., 66) with ``reshape``
+    (reference :144-156)."""
+    if tuple(tensor.shape[-2:]) != (len(_SMPL), 3):
+        raise ValueError(f'map_to_original: (..., 22, 3) expected, got {tuple(tensor.shape)}')
+    mapped = tensor[..., TO_ORIGINAL, :]
+    return mapped.reshape(tuple(mapped.shape[:-2]) + (len(_SMPL) * 3,)) if reshape else mapped
+
+
+_S.map_from_original = staticmethod(map_from_original)       # where the reference's users look for them
+_S.map_to_original = staticmethod(map_to_original)
+
+
 register_skeleton('SMPL_SKELETON', _S, [
     (C.crl_hips__C, _S.Pelvis), (C.crl_spine__C, _S.Spine1), (C.crl_spine01__C, _S.Spine3),
     (C.crl_shoulder__L, _S.L_Collar), (C.crl_arm__L, _S.L_Shoulder), (C.crl_foreArm__L, _S.L_Elbow),

@@ -78,6 +78,9 @@ def add_data_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
     group.add_argument('--transform', type=str, default='hips_neck_bbox')
     group.add_argument('--subsets_dir', type=str, default=None, help='stored subsets of the mixed data modules')
     group.add_argument('--outputs_dir', type=str, default=None, help='where predict mode writes; default: the log directory')
+    group.add_argument('--smpl_carla_targets', action='store_true', default=False,
+                       help='add carla_relative_pose_rot / carla_absolute_pose_rot / carla_absolute_pose_loc to the targets of '
+                            'batches that carry amass_body_pose (one K35 launch per batch)')
     return parser
 
 
@@ -198,7 +201,9 @@ def main(args: Union[List[str], argparse.Namespace], version: Optional[str] = No
                       log_every_n_steps=args.log_every_n_steps, use_graph=bool(args.use_graph and device.type == 'cuda'),
                       device=device, loggers=loggers, callbacks=[checkpoint_callback])
     rank, world = info['rank'], info['world_size']
-    batches = lambda stage: stage_batches(dm, args, device, stage, rank, world)      # noqa: E731
+    from pedestrians_video_2_carla_amd.data.smpl.targets import wrap_smpl_carla_targets
+    batches = lambda stage: wrap_smpl_carla_targets(stage_batches(dm, args, device, stage, rank, world),      # noqa: E731
+                                                    getattr(args, 'smpl_carla_targets', False))
 
     if args.mode in ('train', 'tune'):
         trainer.fit(flow, dm, batches=batches('train'), val_batches=batches('val'),

@@ -3537,6 +3537,58 @@ def _lift_desc(x, weights, biases, skel_type, kind, image, image_is_current, wor
     return d
 
 
+# ---- K35: SMPL body poses (AMASS) -> CARLA bone transforms in one launch (csrc/p2c_smpl.hip) -----------------------------------
+SMPL_CARLA_OUTPUTS = ('relative_pose_rot', 'absolute_pose_loc', 'absolute_pose_rot', 'bones', 'root')
+_SMPL_CARLA_TAIL = {'relative_pose_rot': (J, 3, 3), 'absolute_pose_loc': (J, 3), 'absolute_pose_rot': (J, 3, 3), 'bones': (J, 6),
+                    'root': (6,)}
+
+
+def smpl_framework() -> bool:
+    """P2C_SMPL_FRAMEWORK=1: ``smpl_to_carla`` runs its tensor definition on the device (the comparison arm of
+    tools/bench_smpl_retarget.py)."""
+    return os.environ.get('P2C_SMPL_FRAMEWORK', '0') == '1'
+
+
+@torch.no_grad()
+def smpl_to_carla(body_pose: Tensor, skel_type: Tensor, world_loc: Optional[Tensor] = None, world_rot: Optional[Tensor] = None,
+                  want: Sequence[str] = ('relative_pose_rot', 'absolute_pose_loc', 'absolute_pose_rot'),
+                  max_blocks: int = 0) -> Dict[str, Tensor]:
+    """SMPL body poses as AMASS stores them -> CARLA poses (the reference's ``SMPLDataset.convert_smpl_to_carla``; definition:
+    ``data/smpl/retarget.py``). ``body_pose`` (...,66) or (...,22,3) in original SMPL joint order; ``skel_type`` integer, its shape
+    a prefix of the leading dimensions ((B,) for (B,T,66), (N,) for (N,66)). Returns a dict of the ``want``-ed among
+    ``relative_pose_rot`` (...,26,3,3), ``absolute_pose_loc`` (...,26,3), ``absolute_pose_rot`` (...,26,3,3) and the rows of
+    ``carla_pose_export``: ``bones`` (...,26,6) of (reference locations, ``relative_pose_rot``) and ``root`` (...,6) of
+    ``world_loc`` (...,3) / ``world_rot`` (...,3,3), which come together. A predict / data-time operation: nothing is recorded
+    for autograd. fp32 device tensors outside autocast take K35, one launch whatever is wanted; host tensors, fp64, other
+    dtypes and ``P2C_SMPL_FRAMEWORK=1`` take the tensor definition. ``max_blocks`` lowers the kernel's grid cap (tests)."""
+    from pedestrians_video_2_carla_amd.data.smpl import retarget
+    want = tuple(want)
+    lead = retarget.check_shapes(body_pose, skel_type, world_loc, world_rot, want)
+    floats = [t for t in (body_pose, world_loc, world_rot) if t is not None]
+    if not _carla_kernel_ok(*floats) or smpl_framework():
+        return retarget.convert_smpl_to_carla(body_pose, skel_type, world_loc, world_rot, want)
+    lib = _lib.lib()
+    device = body_pose.device
+    pose = body_pose.detach().reshape(lead + (66,)).contiguous()
+    st = skel_type.detach().to(device=device, dtype=torch.int32).contiguous()
+    wl = world_loc.detach().contiguous() if world_loc is not None else None
+    wr = world_rot.detach().contiguous() if world_rot is not None else None
+    n = pose.numel() // 66
+    frames_per_type = max(n // max(st.numel(), 1), 1)
+    result = {k: torch.empty(lead + _SMPL_CARLA_TAIL[k], dtype=torch.float32, device=device)
+              for k in SMPL_CARLA_OUTPUTS if k in want}
+    if n == 0:
+        return result
+    ref_loc, ref_rot = ref.get_relative_tensors(device)
+    _, ref_abs = ref.get_absolute_tensors(device)
+    with torch.cuda.device(device):
+        _lib.check(lib.p2c_smpl_to_carla_fwd(pose.data_ptr(), st.data_ptr(), frames_per_type, ref_loc.data_ptr(),
+                                             ref_rot.data_ptr(), ref_abs.data_ptr(), _ptr(wl), _ptr(wr),
+                                             *(_ptr(result.get(k)) for k in SMPL_CARLA_OUTPUTS), n, int(max_blocks), _stream()),
+                   'p2c_smpl_to_carla_fwd')
+    return result
+
+
 # ---- K33: decoded video clips -> the pose-estimation flow's input frames (csrc/p2c_frames.hip) ---------------------------------
 FRAMES_MAX_TARGET = 1024             # the largest target size K33 is dispatched for
 
