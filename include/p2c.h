@@ -1130,6 +1130,33 @@ P2C_API int p2c_smpl_to_carla_fwd(const float *body_pose, const int32_t *skel_ty
                                   float *absolute_pose_loc, float *absolute_pose_rot, float *bones, float *root, int64_t N,
                                   int32_t max_blocks, void *stream);
 
+/* ---- K36: 3-D joint locations -> CARLA bone rotations (inverse kinematics) in one launch (csrc/p2c_ik.hip) --------------------
+ * What lets a movements model with the absolute_loc output drive a CARLA walker; the reference has no such step. Definition:
+ * walker_control/inverse_kinematics.py (fit_carla_rotations). N = B T frames, each independent of every other. fp32 in and out,
+ * the fit itself in fp64.
+ *   loc (N,26,3): joint locations in CARLA_SKELETON order; only differences child - bone are read.
+ *   skel_type (N / frames_per_type) int32 on the device, rows of the reference tables; frame n has type
+ *     skel_type[n / frames_per_type]. Not read on the host; a value outside [0, 4) is clamped in the kernel.
+ *   ref_rel_loc (4,26,3), ref_rel_rot (4,26,3,3): the relative reference tables.
+ *   world_loc (N,3), world_rot (N,3,3): both NULL or both given; read for `root` only.
+ * Per bone, parents first, A[parent(root)] = I: P = ref_rel_rot[t][j] A[parent]; a child c is usable when neither its reference
+ * offset nor loc[c] - loc[j] has length zero; no usable child: A[j] = P and relative_pose_rot[j] = ref_rel_rot[t][j] itself; one
+ * child in the tree: A[j] = P S, S the shortest arc from unit(r_c P) to unit(loc[c] - loc[j]) (a half turn about unit(u x e_k), k
+ * the smallest |u_k|, when |u + v|^2 <= 2^-40); several children in the tree: A[j] = the proper rotation maximising
+ * sum_c d_c . (r_c A) over the usable children's unit vectors; then relative_pose_rot[j] = A[j] A[parent]^T.
+ * Outputs, each NULL or given, only the given ones are written: relative_pose_rot (N,26,3,3), absolute_pose_loc (N,26,3) = forward
+ * kinematics of (ref_rel_loc[t], A), absolute_pose_rot (N,26,3,3) = A, bones (N,26,6) = the p2c_carla_pose_fwd row of
+ * (ref_rel_loc[t], relative_pose_rot), root (N,6) = that of (world_loc, world_rot). What is written does not depend on which
+ * others are asked for.
+ * max_blocks  0: the kernel's own grid cap; > 0 lowers it (groups of 32 lanes stride over the frames).
+ * No masking: a non-finite joint goes wherever the arithmetic takes it. One writer per element, nothing reduced: two runs give
+ * the same bits. N = 0: nothing is launched. N < 0, frames_per_type < 1, max_blocks < 0: P2C_E_SHAPE; a missing input, no output at
+ * all, one world input without the other, root without world inputs: P2C_E_NULL; all before any launch. */
+P2C_API int p2c_loc_to_carla_fwd(const float *loc, const int32_t *skel_type, int64_t frames_per_type, const float *ref_rel_loc,
+                                 const float *ref_rel_rot, const float *world_loc, const float *world_rot,
+                                 float *relative_pose_rot, float *absolute_pose_loc, float *absolute_pose_rot, float *bones,
+                                 float *root, int64_t N, int32_t max_blocks, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3589,6 +3589,56 @@ def smpl_to_carla(body_pose: Tensor, skel_type: Tensor, world_loc: Optional[Tens
     return result
 
 
+# ---- K36: 3-D joint locations -> CARLA bone rotations, inverse kinematics in one launch (csrc/p2c_ik.hip) ----------------------
+IK_CARLA_OUTPUTS = ('relative_pose_rot', 'absolute_pose_loc', 'absolute_pose_rot', 'bones', 'root')
+
+
+def ik_framework() -> bool:
+    """P2C_IK_FRAMEWORK=1: ``locations_to_carla`` runs its tensor definition on the device (the comparison arm of
+    tools/bench_ik.py)."""
+    return os.environ.get('P2C_IK_FRAMEWORK', '0') == '1'
+
+
+@torch.no_grad()
+def locations_to_carla(loc: Tensor, skel_type: Tensor, world_loc: Optional[Tensor] = None, world_rot: Optional[Tensor] = None,
+                       want: Sequence[str] = ('relative_pose_rot', 'absolute_pose_loc', 'absolute_pose_rot'),
+                       max_blocks: int = 0) -> Dict[str, Tensor]:
+    """3-D joint locations -> the CARLA pose whose bones point along them (inverse kinematics over the 26-bone tree; definition:
+    ``walker_control/inverse_kinematics.py``). ``loc`` (...,26,3) in ``CARLA_SKELETON`` order; ``skel_type`` integer, its shape a
+    prefix of the leading dimensions ((B,) for (B,T,26,3), (N,) for (N,26,3)). Returns a dict of the ``want``-ed among
+    ``relative_pose_rot`` (...,26,3,3), ``absolute_pose_loc`` (...,26,3) (the pose re-targeted to the reference bone lengths),
+    ``absolute_pose_rot`` (...,26,3,3) and the rows of ``carla_pose_export``: ``bones`` (...,26,6) of (reference locations,
+    ``relative_pose_rot``) and ``root`` (...,6) of ``world_loc`` (...,3) / ``world_rot`` (...,3,3), which come together. A predict-time
+    operation: nothing is recorded for autograd. fp32 device tensors outside autocast take K36, one launch whatever is wanted;
+    host tensors, fp64, other dtypes and ``P2C_IK_FRAMEWORK=1`` take the tensor definition on the tensor's device.
+    ``max_blocks`` lowers the kernel's grid cap (tests)."""
+    from pedestrians_video_2_carla_amd.walker_control import inverse_kinematics as ik
+    want = tuple(want)
+    lead = ik.check_shapes(loc, skel_type, world_loc, world_rot, want)
+    floats = [t for t in (loc, world_loc, world_rot) if t is not None]
+    if not _carla_kernel_ok(*floats) or ik_framework():
+        return ik.fit_carla_rotations(loc, skel_type, world_loc, world_rot, want)
+    lib = _lib.lib()
+    device = loc.device
+    x = loc.detach().contiguous()
+    st = skel_type.detach().to(device=device, dtype=torch.int32).contiguous()
+    wl = world_loc.detach().contiguous() if world_loc is not None else None
+    wr = world_rot.detach().contiguous() if world_rot is not None else None
+    n = x.numel() // (J * 3)
+    frames_per_type = max(n // max(st.numel(), 1), 1)
+    result = {k: torch.empty(lead + _SMPL_CARLA_TAIL[k], dtype=torch.float32, device=device)
+              for k in IK_CARLA_OUTPUTS if k in want}
+    if n == 0:
+        return result
+    ref_loc, ref_rot = ref.get_relative_tensors(device)
+    with torch.cuda.device(device):
+        _lib.check(lib.p2c_loc_to_carla_fwd(x.data_ptr(), st.data_ptr(), frames_per_type, ref_loc.data_ptr(), ref_rot.data_ptr(),
+                                            _ptr(wl), _ptr(wr), *(_ptr(result.get(k)) for k in IK_CARLA_OUTPUTS), n,
+                                            int(max_blocks), _stream()),
+                   'p2c_loc_to_carla_fwd')
+    return result
+
+
 # ---- K33: decoded video clips -> the pose-estimation flow's input frames (csrc/p2c_frames.hip) ---------------------------------
 FRAMES_MAX_TARGET = 1024             # the largest target size K33 is dispatched for
 

@@ -829,17 +829,25 @@ class Trainer:
         finally:
             flow.train(was_training)
 
-    def predict_carla(self, flow, batches: Iterable) -> List:
+    def predict_carla(self, flow, batches: Iterable, ik: bool = False) -> List:
         """The predict loop for a CARLA player: per batch ``(bones (B,T,26,6), root (B,T,6), meta)``, the rows
         ``export_clips(flow.predict_step(batch))`` would give, left on the batch's device. A LinearAE flow takes one launch per
-        batch (K32, ``walker_control.carla_lifter.CarlaLifter``); other movements models the composed path. Eval mode, no
-        gradients, the flow's train / eval mode is put back afterwards."""
+        batch (K32, ``walker_control.carla_lifter.CarlaLifter``); other movements models the composed path. A movements model
+        that outputs absolute locations has no bone rotations to export and raises ``KeyError``; with ``ik=True`` such a flow
+        goes through ``walker_control.location_retargeter.LocationRetargeter`` instead: model -> pose head -> the rotations
+        fitted to the predicted locations (K36, one launch per batch). Eval mode, no gradients, the flow's train / eval mode is
+        put back afterwards."""
         from pedestrians_video_2_carla_amd.walker_control.carla_lifter import CarlaLifter
         lifter = CarlaLifter(flow)
         was_training = flow.training
         flow.eval()
         try:
             with torch.no_grad():
+                if ik and lifter.kind is None:
+                    from pedestrians_video_2_carla_amd.walker_control.location_retargeter import LocationRetargeter
+                    fit = LocationRetargeter()
+                    fit.check_flow(flow)
+                    return [(*fit.lift(flow, batch), batch[2]) for batch in batches]
                 return [(*lifter.lift(batch[0], batch[2]), batch[2]) for batch in batches]
         finally:
             flow.train(was_training)

@@ -1,0 +1,182 @@
+"""3-D joint locations -> CARLA bone rotations: the tensor definition of K36 (inverse kinematics over the 26-bone tree).
+
+The movements models with the ``absolute_loc`` output (PoseFormer, Baseline3DPose, LinearAE / Seq2Seq with
+``--movements_output_type absolute_loc``) leave ``absolute_pose_loc`` only, and everything that a CARLA walker can play
+(``ops.carla_pose_export``, ``CarlaPose``, ``save_carla_animation``) needs relative bone rotations. ``fit_carla_rotations`` finds
+the ``relative_pose_rot`` whose forward kinematics puts the reference skeleton's bones along the observed ones. The reference
+project has no such step. Row-vector convention of ``data/carla/reference.forward_kinematics``:
+
+    abs_rot[j] = rel_rot[j] @ abs_rot[parent],   abs_loc[j] = rel_loc[j] @ abs_rot[parent] + abs_loc[parent].
+
+Symbols: ``R_ref``, ``r`` = ``ref.get_relative_tensors`` of the frame's type, ``X`` the input, ``A[j]`` the fitted absolute
+rotation (``A[parent(root)] = I``). Only differences ``X[c] - X[j]`` are read: a fit of directions, blind to translation, uniform
+scale and bone lengths. Per bone, parents first:
+
+* prior ``P = R_ref[j] @ A[parent]``: where the bone points if it keeps its reference relative rotation;
+* a child c is usable when neither ``|r_c|`` nor ``|X[c] - X[j]|`` is zero (a NaN length is not zero: nothing is masked, a
+  non-finite joint goes wherever the arithmetic takes it). The hips' offset from the root is zero in all four skeletons: the root
+  never has a usable child;
+* no usable child (the leaves, the root, coincident joints such as zero-padded frames): ``A[j] = P`` and ``relative_pose_rot[j]``
+  is the table row ``R_ref[j]`` itself, copied;
+* one child in the tree, usable: ``u = unit(r_c @ P)``, ``v = unit(X[c] - X[j])``, ``S`` the shortest-arc rotation with
+  ``u S = v`` -- from the half vector ``h = unit(u + v)``: the transposed matrix of the quaternion ``(u . h, u x h)``; when
+  ``|u + v|^2 <= 2^-40`` the half turn ``2 a^T a - I`` about ``a = unit(u x e_k)``, k the index of the smallest ``|u_k|`` (lowest
+  on ties) -- and ``A[j] = P @ S``. The twist about the bone comes from the prior alone: no state, no flips between frames;
+* several children in the tree (hips, spine01, head), at least one usable: ``A[j]`` = the proper rotation maximising
+  ``sum_c d_c . (r_c A)`` over the usable children's unit vectors: orthogonal Procrustes of ``H[a][b] = sum_c d_c[a] r_c[b]``
+  (an SVD with the determinant fix of ``metrics/extra_metrics.p_mpjpe`` here, ``p2c_procrustes::solve`` in the kernel). A
+  non-finite ``H`` gives NaN. With fewer than two non-collinear usable children the answer is some finite proper rotation;
+* where a fit happened, ``relative_pose_rot[j] = A[j] @ A[parent]^T``.
+
+``absolute_pose_rot = A``; ``absolute_pose_loc`` = forward kinematics of ``(r, A)``: the input pose re-targeted to the reference
+bone lengths; ``bones`` / ``root`` = the rows of ``ops.carla_pose_export`` of ``(r, relative_pose_rot)`` / ``(world_loc, world_rot)``.
+"""
+from typing import Dict, Optional, Sequence
+
+import torch
+from torch import Tensor
+
+from pedestrians_video_2_carla_amd.data.carla import reference as ref
+from pedestrians_video_2_carla_amd.data.carla.skeleton import CARLA_SKELETON, PARENTS
+
+POSE_KEYS = ('relative_pose_rot', 'absolute_pose_loc', 'absolute_pose_rot')
+ROW_KEYS = ('bones', 'root')
+J = len(CARLA_SKELETON)
+CHILDREN = tuple(tuple(c for c, p in enumerate(PARENTS) if p == j) for j in range(J))
+ANTIPARALLEL_EPS = 2.0 ** -40          # |u + v|^2 at or below which the shortest arc is the half turn
+
+
+def check_shapes(loc: Tensor, skel_type: Tensor, world_loc: Optional[Tensor], world_rot: Optional[Tensor],
+                 want: Sequence[str]):
+    """-> the leading dimensions of ``loc`` (..., 26, 3); raises on anything that does not fit them (the checks of
+    ``data/smpl/retarget.check_shapes``)."""
+    if loc.ndim < 2 or tuple(loc.shape[-2:]) != (J, 3):
+        raise RuntimeError(f'locations_to_carla: loc (..., {J}, 3) expected, got {tuple(loc.shape)}')
+    if not loc.is_floating_point():
+        raise RuntimeError(f'locations_to_carla: loc holds coordinates: a floating tensor expected, got {loc.dtype}')
+    lead = tuple(loc.shape[:-2])
+    if skel_type.is_floating_point() or skel_type.dtype == torch.bool:
+        raise RuntimeError(f'locations_to_carla: skel_type holds table rows: an integer tensor expected, got {skel_type.dtype}')
+    if not lead or tuple(skel_type.shape) != lead[:skel_type.ndim] or skel_type.ndim < 1:
+        raise RuntimeError(f'locations_to_carla: skel_type {tuple(skel_type.shape)} is not a prefix of the leading dimensions {lead}')
+    unknown = [k for k in want if k not in POSE_KEYS + ROW_KEYS]
+    if unknown or not want:
+        raise RuntimeError(f'locations_to_carla: want {tuple(want)}; a non-empty choice of {POSE_KEYS + ROW_KEYS} expected')
+    if (world_loc is None) != (world_rot is None):
+        raise RuntimeError('locations_to_carla: world_loc and world_rot come together or not at all')
+    if world_loc is not None and (tuple(world_loc.shape) != lead + (3,) or tuple(world_rot.shape) != lead + (3, 3)):
+        raise RuntimeError(f'locations_to_carla: world tensors {tuple(world_loc.shape)}, {tuple(world_rot.shape)}; '
+                           f'{lead + (3,)} and {lead + (3, 3)} expected')
+    if 'root' in want and world_loc is None:
+        raise RuntimeError("locations_to_carla: 'root' needs world_loc and world_rot")
+    return lead
+
+
+def _carla_row(loc: Tensor, rot: Tensor) -> Tensor:
+    from pedestrians_video_2_carla_amd.ops import _carla_row as row
+    return row(loc, rot)
+
+
+def quaternion_rows(q0: Tensor, qx: Tensor, qy: Tensor, qz: Tensor) -> Tensor:
+    """The transposed matrix of the quaternion (q0, qx, qy, qz): ``x S`` turns the row vector x as the quaternion turns a column."""
+    rows = (q0 * q0 + qx * qx - qy * qy - qz * qz, 2.0 * (qy * qx + q0 * qz), 2.0 * (qz * qx - q0 * qy),
+            2.0 * (qx * qy - q0 * qz), q0 * q0 - qx * qx + qy * qy - qz * qz, 2.0 * (qz * qy + q0 * qx),
+            2.0 * (qx * qz + q0 * qy), 2.0 * (qy * qz - q0 * qx), q0 * q0 - qx * qx - qy * qy + qz * qz)
+    return torch.stack(rows, -1).reshape(q0.shape + (3, 3))
+
+
+def shortest_arc(u: Tensor, v: Tensor) -> Tensor:
+    """Unit vectors (..., 3) -> S (..., 3, 3), the rotation by the smaller angle in the plane of u and v, with ``u S = v``."""
+    s = u + v
+    s2 = (s * s).sum(-1)
+    flip = s2 <= ANTIPARALLEL_EPS                                      # False for NaN: a NaN runs the half-vector form
+    h = s / torch.where(flip, torch.ones_like(s2), s2).sqrt().unsqueeze(-1)
+    arc = quaternion_rows((u * h).sum(-1), *torch.linalg.cross(u, h).unbind(-1))
+    # the half turn about an axis at right angles to u: u x e_k for the smallest |u_k|, the best-conditioned of the three
+    mag = u.abs()
+    k = torch.where((mag[..., 0] <= mag[..., 1]) & (mag[..., 0] <= mag[..., 2]), 0, torch.where(mag[..., 1] <= mag[..., 2], 1, 2))
+    e = torch.nn.functional.one_hot(k, 3).to(u.dtype)
+    a = torch.linalg.cross(u, e)
+    a = a / (a * a).sum(-1, keepdim=True).sqrt()
+    turn = 2.0 * a.unsqueeze(-1) * a.unsqueeze(-2) - torch.eye(3, dtype=u.dtype, device=u.device)
+    return torch.where(flip[..., None, None], turn, arc)
+
+
+def procrustes(H: Tensor) -> Tensor:
+    """``H`` (..., 3, 3) -> the proper rotation R maximising ``tr(H R)`` (``p_mpjpe``'s: H = U S V^T, R = V U^T, the smallest
+    singular direction flipped when det R < 0). A non-finite H gives NaN."""
+    finite = torch.isfinite(H).all(-1).all(-1)
+    eye = torch.eye(3, dtype=H.dtype, device=H.device)
+    U, _, Vt = torch.linalg.svd(torch.where(finite[..., None, None], H, eye))
+    V = Vt.transpose(-1, -2)
+    sign = torch.sign(torch.linalg.det(V @ U.transpose(-1, -2)))
+    V = torch.cat((V[..., :, :-1], V[..., :, -1:] * sign[..., None, None]), -1)
+    R = V @ U.transpose(-1, -2)
+    return torch.where(finite[..., None, None], R, torch.full_like(R, float('nan')))
+
+
+def _unit(x: Tensor):
+    """(vector / its length, length is not zero); a zero vector stays zero."""
+    n = (x * x).sum(-1).sqrt()
+    ok = ~(n == 0)
+    return x / torch.where(ok, n, torch.ones_like(n)).unsqueeze(-1), ok
+
+
+@torch.no_grad()
+def fit_carla_rotations(loc: Tensor, skel_type: Tensor, world_loc: Optional[Tensor] = None,
+                        world_rot: Optional[Tensor] = None, want: Sequence[str] = POSE_KEYS) -> Dict[str, Tensor]:
+    """``loc`` (..., 26, 3) in ``CARLA_SKELETON`` order, ``skel_type`` integer with a shape that is a prefix of the leading
+    dimensions (rows of ``CARLA_REFERENCE_SKELETON_TYPES``) -> dict of the ``want``-ed among ``relative_pose_rot`` (..., 26, 3, 3),
+    ``absolute_pose_loc`` (..., 26, 3), ``absolute_pose_rot`` (..., 26, 3, 3), ``bones`` (..., 26, 6) and ``root`` (..., 6) (the rows
+    of ``ops.carla_pose_export``; ``root`` from ``world_loc`` / ``world_rot``). Tensor ops, the dtype of ``loc``."""
+    want = tuple(want)
+    lead = check_shapes(loc, skel_type, world_loc, world_rot, want)
+    dtype, device = loc.dtype, loc.device
+    st = skel_type.to(device=device, dtype=torch.long).reshape(tuple(skel_type.shape) + (1,) * (len(lead) - skel_type.ndim))
+    st = st.expand(lead)
+    rel_loc, ref_rot = (t[st] for t in ref.get_relative_tensors(device, dtype=dtype))
+
+    A, rel, a_loc = [None] * J, [None] * J, [None] * J
+    for j, parent in enumerate(PARENTS):
+        prior = ref_rot[..., j, :, :] if parent < 0 else ref_rot[..., j, :, :] @ A[parent]
+        a_loc[j] = rel_loc[..., j, :] if parent < 0 else (rel_loc[..., j, None, :] @ A[parent])[..., 0, :] + a_loc[parent]
+        fitted, any_usable = None, None
+        if len(CHILDREN[j]) == 1:
+            c = CHILDREN[j][0]
+            r_hat, r_ok = _unit(rel_loc[..., c, :])
+            v, d_ok = _unit(loc[..., c, :] - loc[..., j, :])
+            any_usable = r_ok & d_ok
+            # |r_c @ P| = |r_c| up to rounding: u is normalised again, as the definition says
+            u, _ = _unit((r_hat.unsqueeze(-2) @ prior)[..., 0, :])
+            fitted = prior @ shortest_arc(u, v)
+        elif len(CHILDREN[j]) > 1:
+            H = torch.zeros(lead + (3, 3), dtype=dtype, device=device)
+            any_usable = torch.zeros(lead, dtype=torch.bool, device=device)
+            for c in CHILDREN[j]:
+                r_hat, r_ok = _unit(rel_loc[..., c, :])
+                d_hat, d_ok = _unit(loc[..., c, :] - loc[..., j, :])
+                usable = r_ok & d_ok
+                H = H + torch.where(usable[..., None, None], d_hat.unsqueeze(-1) * r_hat.unsqueeze(-2), torch.zeros_like(H))
+                any_usable = any_usable | usable
+            fitted = procrustes(H)
+        if fitted is None:
+            A[j], rel[j] = prior, ref_rot[..., j, :, :]
+        else:
+            m = any_usable[..., None, None]
+            A[j] = torch.where(m, fitted, prior)
+            moved = fitted if parent < 0 else fitted @ A[parent].transpose(-1, -2)
+            rel[j] = torch.where(m, moved, ref_rot[..., j, :, :])
+
+    out = {}
+    relative_pose_rot = torch.stack(rel, -3)
+    if 'relative_pose_rot' in want:
+        out['relative_pose_rot'] = relative_pose_rot
+    if 'absolute_pose_loc' in want:
+        out['absolute_pose_loc'] = torch.stack(a_loc, -2)
+    if 'absolute_pose_rot' in want:
+        out['absolute_pose_rot'] = torch.stack(A, -3)
+    if 'bones' in want:
+        out['bones'] = _carla_row(rel_loc, relative_pose_rot)
+    if 'root' in want:
+        out['root'] = _carla_row(world_loc.to(dtype), world_rot.to(dtype))
+    return out
