@@ -11,6 +11,12 @@ inline int launch_status() {
   return e == hipSuccess ? 0 : (int)e;
 }
 
+// The grid of a kernel whose workgroups stride over `want` units of work: capped at `limit`, which max_blocks > 0 lowers.
+inline unsigned grid_for(int64_t want, int32_t max_blocks, int limit) {
+  const int cap = max_blocks > 0 && max_blocks < limit ? max_blocks : limit;
+  return (unsigned)(want < cap ? want : cap);
+}
+
 // Every pointer is 16-byte aligned (float4 loads and stores). A null pointer passes: an optional tensor that is absent.
 template <class... P>
 inline bool aligned16(const P *...p) {

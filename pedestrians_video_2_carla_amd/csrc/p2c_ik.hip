@@ -16,13 +16,13 @@
 //   root = the K30 row of (world_loc, world_rot).
 // Only differences of X are read: a fit of directions. Nothing accumulates over frames.
 //
-// Mapping (K35's lanes). A bone per lane, 32 lanes per frame, two frames (a pair) per wavefront at a time. Lanes 0..25 are the
-// bones in CARLA_SKELETON (= DFS) order, lane 26 holds the identity the root composes with and, with world inputs, writes the
-// root row; lanes 27..31 idle. A wavefront takes a chunk of `pairs` consecutive pairs (1 .. 10, chosen on the host from N alone);
-// chunks stride over the frames (grid capped at kMaxBlocks workgroups of four wavefronts, max_blocks lowers the cap).
+// Mapping. The frame group of p2c_carla_dev.h (frame_lane: a bone per lane, 32 lanes per frame), two frames (a pair) per
+// wavefront at a time. The group's spare lane holds the identity the root composes with and, with world inputs, writes the root
+// row (store_rows). A wavefront takes a chunk of `pairs` consecutive pairs (1 .. 10, chosen on the host from N alone);
+// chunks stride over the frames (grid capped at kFrameMaxBlocks workgroups of four wavefronts, max_blocks lowers the cap).
 //   * Loads. A lane reads its own joint's 12 bytes (a pair is one 624-byte span) and its bone's 12 floats of the two (4,26,..)
-//     tables (5 KB in all: cache resident) after the frame's skeleton type, one broadcast load per group; a type outside [0, 4)
-//     is clamped, never followed.
+//     tables (load_ref; 5 KB in all: cache resident) after the frame's skeleton type (frame_type: one broadcast load per group,
+//     clamped, never followed).
 //   * Children. Up to three per bone; their locations and reference offsets come across lanes (ds_bpermute, fp32, 18 moves).
 //   * Procrustes first, and together. The absolute rotation of a bone with several children does not depend on its parent, so
 //     the solves come out of the tree walk; and only 3 lanes in 32 have one, so a chunk gathers them: phase 1 forms H for every
@@ -57,13 +57,12 @@
 namespace p2c_ik {
 
 namespace ph = p2c;
+namespace pc = p2c_carla;
 constexpr int J = ph::J;
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 2048;   // 8 workgroups per CU on 256 CUs
+constexpr int kThreads = pc::kFrameThreads;
 constexpr int kMaxPairs = 10;      // frame pairs per wavefront and pass: 6 Procrustes solves each, 60 of the 64 lanes
 constexpr int kSpreadFrames = 2048;   // one wavefront per SIMD (1024) times two frames
-constexpr int kTypes = 4;
-constexpr int kLevels = 8;         // root .. hand
+constexpr int kLevels = 8;        // root .. hand
 constexpr double kAntiparallel = 0x1p-40;
 
 // depth of each bone in the tree (idle lanes: no level), its number of children, and the children's lanes (-1: none)
@@ -150,9 +149,9 @@ struct Args {
   int32_t pairs;                 // frame pairs a wavefront takes at a time: 1 .. kMaxPairs
 };
 
-struct LaneConsts {
-  int lane, j, base, jb, parent, depth, ch[3];
-  bool bone, spare, multi;
+struct LaneConsts : pc::FrameLane {
+  int parent, depth, ch[3];
+  bool multi;
 };
 
 // this lane's joint, the frame's skeleton type, the bone's reference rows, the children's unit offsets (every lane of the
@@ -169,17 +168,9 @@ __device__ __forceinline__ void read_frame(const Args &a, const LaneConsts &L, i
       const float *p = a.loc + (n * J + L.j) * 3;
       x0 = p[0], x1 = p[1], x2 = p[2];
     }
-    const int64_t clip = a.frames_per_type == 1 ? n
-                         : (n <= 0xffffffffll ? (int64_t)((uint32_t)n / (uint32_t)a.frames_per_type) : n / a.frames_per_type);
-    st = a.skel_type[clip];
-    st = st < 0 ? 0 : (st >= kTypes ? kTypes - 1 : st);
+    st = pc::frame_type(a.skel_type, n, a.frames_per_type);
   }
-  const size_t row = (size_t)st * J + L.jb;
-  const float *pr = a.ref_rel_rot + row * 9;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) q[i] = pr[i];
-  const float *pl = a.ref_rel_loc + row * 3;
-  l0 = pl[0], l1 = pl[1], l2 = pl[2];
+  pc::load_ref(a.ref_rel_rot, a.ref_rel_loc, (size_t)st * J + L.jb, q, l0, l1, l2);
 
 #pragma unroll
   for (int i = 0; i < 9; ++i) H[i] = 0.0;
@@ -205,9 +196,7 @@ __device__ __forceinline__ void read_frame(const Args &a, const LaneConsts &L, i
 
 __global__ __launch_bounds__(kThreads) void loc_to_carla_kernel(const Args a) {
   LaneConsts L;
-  L.lane = threadIdx.x & 63, L.j = L.lane & 31, L.base = L.lane & 32;
-  L.bone = L.j < J, L.spare = L.j == ph::IDL;
-  L.jb = L.bone ? L.j : 0;                             // the table row an idle lane reads (and never uses)
+  static_cast<pc::FrameLane &>(L) = pc::frame_lane();
   L.parent = L.base + ph::c_parent[L.j];               // root and idle lanes: the identity lane / themselves
   L.depth = c_depth[L.j];
   L.ch[0] = c_child[0][L.j], L.ch[1] = c_child[1][L.j], L.ch[2] = c_child[2][L.j];
@@ -309,25 +298,8 @@ __global__ __launch_bounds__(kThreads) void loc_to_carla_kernel(const Args a) {
         float *o = a.abs_loc + ((size_t)n * J + j) * 3;
         o[0] = (float)al.x, o[1] = (float)al.y, o[2] = (float)al.z;
       }
-      // rows: bones by their lanes, the root row by the spare lane
-      if (a.bones || a.root) {
-        float x = l0, y = l1, z = l2, r00 = f0, r01 = f1, r02 = f2, r12 = f5, r22 = f8;
-        const bool root = L.spare && a.root;
-        if (root) {
-          const float *w = a.world_loc + n * 3, *r = a.world_rot + n * 9;
-          x = w[0], y = w[1], z = w[2];
-          r00 = r[0], r01 = r[1], r02 = r[2], r12 = r[5], r22 = r[8];
-        }
-        float o[6];
-        p2c_carla::carla_row(x, y, z, r00, r01, r02, r12, r22, o);
-        float *dst = nullptr;
-        if (L.bone && a.bones) dst = a.bones + ((size_t)n * J + j) * 6;
-        if (root) dst = a.root + (size_t)n * 6;
-        if (dst) {
-#pragma unroll
-          for (int k = 0; k < 6; ++k) dst[k] = o[k];
-        }
-      }
+      // rows: p2c_carla::carla_row(table offset, rounded relative rotation) by the bone lanes, the world's by the spare lane
+      pc::store_rows(a.bones, a.root, a.world_loc, a.world_rot, n, L, l0, l1, l2, f0, f1, f2, f5, f8);
     }
   }
 }
@@ -340,12 +312,10 @@ extern "C" int p2c_loc_to_carla_fwd(const float *loc, const int32_t *skel_type, 
                                     const float *ref_rel_rot, const float *world_loc, const float *world_rot,
                                     float *relative_pose_rot, float *absolute_pose_loc, float *absolute_pose_rot, float *bones,
                                     float *root, int64_t N, int32_t max_blocks, void *stream) {
-  if (N < 0 || N > ((int64_t)1 << 40) || frames_per_type < 1 || frames_per_type > 0x7fffffff || max_blocks < 0) return P2C_E_SHAPE;
-  if (!loc || !skel_type || !ref_rel_loc || !ref_rel_rot) return P2C_E_NULL;
-  if (!relative_pose_rot && !absolute_pose_loc && !absolute_pose_rot && !bones && !root) return P2C_E_NULL;
-  if ((world_loc == nullptr) != (world_rot == nullptr)) return P2C_E_NULL;      // both or neither
-  if (root && !world_loc) return P2C_E_NULL;
-  if (N == 0) return 0;
+  const int rc = pc::check_frames_call(N, frames_per_type, max_blocks, loc && skel_type && ref_rel_loc && ref_rel_rot,
+                                       relative_pose_rot || absolute_pose_loc || absolute_pose_rot || bones || root, world_loc,
+                                       world_rot, root);
+  if (rc || N == 0) return rc;
   Args a{};
   a.loc = loc, a.skel_type = skel_type;
   a.ref_rel_loc = ref_rel_loc, a.ref_rel_rot = ref_rel_rot;
@@ -356,9 +326,8 @@ extern "C" int p2c_loc_to_carla_fwd(const float *loc, const int32_t *skel_type, 
   // more pairs at a time and their Procrustes solves share one pass
   const int64_t pairs = (N + kSpreadFrames - 1) / kSpreadFrames;
   a.pairs = (int32_t)(pairs < 1 ? 1 : (pairs > kMaxPairs ? kMaxPairs : pairs));
-  const int cap = max_blocks > 0 && max_blocks < kMaxBlocks ? max_blocks : kMaxBlocks;
   const int64_t chunks = (N + 2 * a.pairs - 1) / (2 * a.pairs);
-  const int64_t want = (chunks + kThreads / 64 - 1) / (kThreads / 64);
-  hipLaunchKernelGGL(loc_to_carla_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(kThreads), 0, (hipStream_t)stream, a);
+  const unsigned grid = p2c_host::grid_for((chunks + kThreads / 64 - 1) / (kThreads / 64), max_blocks, pc::kFrameMaxBlocks);
+  hipLaunchKernelGGL(loc_to_carla_kernel, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, a);
   return p2c_host::launch_status();
 }

@@ -11,15 +11,15 @@
 //   bones = the K30 row of (ref_rel_loc[t], relative_pose_rot), root = the K30 row of (world_loc, world_rot).
 // No masking: a NaN joint reaches its bone and the bone's descendants. Nothing accumulates over frames.
 //
-// Mapping. A bone per lane, 32 lanes per frame, two frames per wavefront, eight per workgroup; groups stride over the frames
-// (grid capped at kMaxBlocks workgroups, max_blocks lowers the cap). Lanes 0..25 are the bones in CARLA_SKELETON (= DFS) order,
-// lane 26 is the group's spare: it converts Spine2 -- the SMPL joint no bone owns -- and, with world inputs, writes the root row;
-// for the forward kinematics it is the identity lane of the pose head's tree walk. Lanes 27..31 idle.
+// Mapping. The frame group of p2c_carla_dev.h (frame_lane: a bone per lane, 32 lanes per frame), two frames per wavefront, eight
+// per workgroup; groups stride over the frames (grid capped at kFrameMaxBlocks workgroups, max_blocks lowers the cap). The group's
+// spare lane converts Spine2 -- the SMPL joint no bone owns -- and, with world inputs, writes the root row (store_rows); for the
+// forward kinematics it is the identity lane of the pose head's tree walk.
 //   * Frame loads. Every one of the 22 SMPL joints belongs to exactly one lane (21 bones + the spare), which reads its own 12
 //     bytes: the 22 loads of a group cover the frame's 264 bytes once and a wavefront's two frames are one 528-byte span. No
 //     staging: nothing is read twice. Only M[Spine2] changes lanes (spare -> spine01, nine ds_bpermute).
 //   * Tables. A lane reads its bone's 21 floats of the three (4,26,..) reference tables (8.7 KB in all: cache resident) after
-//     the frame's skeleton type, one broadcast load per group; a type outside [0, 4) is clamped, never followed.
+//     the frame's skeleton type (frame_type: one broadcast load per group, clamped, never followed).
 //   * Forward kinematics. fk_doubling of p2c_pose_head_dev.h: pointer doubling in three rounds instead of eight dependent
 //     levels -- DPP row_shr:1 where the parent is the previous lane, ds_bpermute for the two ancestor rounds. Both stay in
 //     registers: no LDS allocation, no barrier (a frame's lanes sit in one wavefront), and no LDS for the poison audit to find.
@@ -42,11 +42,9 @@
 namespace p2c_smpl {
 
 namespace ph = p2c;
+namespace pc = p2c_carla;
 constexpr int J = ph::J;
-constexpr int kThreads = 256;
-constexpr int kFramesPerBlock = kThreads / ph::GROUP;
-constexpr int kMaxBlocks = 2048;   // 8 workgroups per CU on 256 CUs
-constexpr int kTypes = 4;
+constexpr int kFramesPerBlock = pc::kFrameThreads / ph::GROUP;
 constexpr int kSmplValues = 66;
 
 // lane -> the ORIGINAL-order SMPL joint it converts (-1: none). Lanes 0..25: the 21 pairs of get_common_indices(SMPL_SKELETON);
@@ -64,16 +62,15 @@ struct Args {
   int32_t frames_per_type;
 };
 
-__global__ __launch_bounds__(kThreads) void smpl_to_carla_kernel(const Args a) {
+__global__ __launch_bounds__(pc::kFrameThreads) void smpl_to_carla_kernel(const Args a) {
+  const pc::FrameLane F = pc::frame_lane();
   ph::LaneCtx L;
-  L.lane = threadIdx.x & 63, L.j = L.lane & 31, L.base = L.lane & 32;
+  L.lane = F.lane, L.j = F.j, L.base = F.base;
   L.anc0 = ph::c_parent[L.j], L.anc1 = ph::c_anc_r2[L.j], L.anc2 = ph::c_anc_r3[L.j];
   L.interior = (ph::kInteriorMask >> L.j) & 1u;
-  const bool bone = L.j < J, spare = L.j == ph::IDL;
+  const bool bone = F.bone;
   const int sj = c_smpl_joint[L.j];
-  const int jb = bone ? L.j : 0;                       // the table row an idle lane reads (and never uses)
   const bool want_fk = a.abs_loc || a.abs_rot;
-  const bool want_rows = a.bones || a.root;
 
   const int64_t step = (int64_t)gridDim.x * kFramesPerBlock;
   for (int64_t n = (int64_t)blockIdx.x * kFramesPerBlock + (threadIdx.x >> 5); n < a.N; n += step) {
@@ -83,21 +80,15 @@ __global__ __launch_bounds__(kThreads) void smpl_to_carla_kernel(const Args a) {
       const float *p = a.body_pose + n * kSmplValues + sj * 3;
       p0 = p[0], p1 = p[1], p2 = p[2];
     }
-    const int64_t clip = a.frames_per_type == 1 ? n
-                         : (n <= 0xffffffffll ? (int64_t)((uint32_t)n / (uint32_t)a.frames_per_type) : n / a.frames_per_type);
-    int st = a.skel_type[clip];
-    st = st < 0 ? 0 : (st >= kTypes ? kTypes - 1 : st);
-    const size_t row = (size_t)st * J + jb;
+    const size_t row = (size_t)pc::frame_type(a.skel_type, n, a.frames_per_type) * J + F.jb;
     ph::M3 R0, Lm;
+    ph::V3 l0;
+    pc::load_ref(a.ref_rel_rot, a.ref_rel_loc, row, R0.m, l0.x, l0.y, l0.z);
     {
-      const float *pr = a.ref_rel_rot + row * 9, *pa = a.ref_abs_rot + row * 9;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) R0.m[i] = pr[i];
+      const float *pa = a.ref_abs_rot + row * 9;
 #pragma unroll
       for (int i = 0; i < 3; ++i) Lm.m[i * 3 + 0] = pa[i * 3 + 0], Lm.m[i * 3 + 1] = pa[i * 3 + 2], Lm.m[i * 3 + 2] = -pa[i * 3 + 1];
     }
-    const float *pl = a.ref_rel_loc + row * 3;
-    ph::V3 l0 = ph::v3(pl[0], pl[1], pl[2]);
 
     // ---- M = Rx Ry Rz of (-p0, p1, p2) ----
     float s0, c0, s1, c1, s2, c2;
@@ -125,24 +116,7 @@ __global__ __launch_bounds__(kThreads) void smpl_to_carla_kernel(const Args a) {
     if (bone && a.rel_rot) ph::store_m3(a.rel_rot, (size_t)n * J + L.j, R);
 
     // ---- rows: bones by their lanes, the root row by the spare lane ----
-    if (want_rows) {
-      float x = l0.x, y = l0.y, z = l0.z, r00 = R.m[0], r01 = R.m[1], r02 = R.m[2], r12 = R.m[5], r22 = R.m[8];
-      const bool root = spare && a.root;
-      if (root) {
-        const float *w = a.world_loc + n * 3, *r = a.world_rot + n * 9;
-        x = w[0], y = w[1], z = w[2];
-        r00 = r[0], r01 = r[1], r02 = r[2], r12 = r[5], r22 = r[8];
-      }
-      float o[6];
-      p2c_carla::carla_row(x, y, z, r00, r01, r02, r12, r22, o);
-      float *dst = nullptr;
-      if (bone && a.bones) dst = a.bones + ((size_t)n * J + L.j) * 6;
-      if (root) dst = a.root + (size_t)n * 6;
-      if (dst) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) dst[i] = o[i];
-      }
-    }
+    pc::store_rows(a.bones, a.root, a.world_loc, a.world_rot, n, F, l0.x, l0.y, l0.z, R.m[0], R.m[1], R.m[2], R.m[5], R.m[8]);
 
     // ---- forward kinematics over the group ----
     if (want_fk) {
@@ -166,20 +140,17 @@ extern "C" int p2c_smpl_to_carla_fwd(const float *body_pose, const int32_t *skel
                                      const float *world_loc, const float *world_rot, float *relative_pose_rot,
                                      float *absolute_pose_loc, float *absolute_pose_rot, float *bones, float *root, int64_t N,
                                      int32_t max_blocks, void *stream) {
-  if (N < 0 || N > ((int64_t)1 << 40) || frames_per_type < 1 || frames_per_type > 0x7fffffff || max_blocks < 0) return P2C_E_SHAPE;
-  if (!body_pose || !skel_type || !ref_rel_loc || !ref_rel_rot || !ref_abs_rot) return P2C_E_NULL;
-  if (!relative_pose_rot && !absolute_pose_loc && !absolute_pose_rot && !bones && !root) return P2C_E_NULL;
-  if ((world_loc == nullptr) != (world_rot == nullptr)) return P2C_E_NULL;      // both or neither
-  if (root && !world_loc) return P2C_E_NULL;
-  if (N == 0) return 0;
+  const int rc = pc::check_frames_call(N, frames_per_type, max_blocks, body_pose && skel_type && ref_rel_loc && ref_rel_rot && ref_abs_rot,
+                                       relative_pose_rot || absolute_pose_loc || absolute_pose_rot || bones || root, world_loc,
+                                       world_rot, root);
+  if (rc || N == 0) return rc;
   Args a{};
   a.body_pose = body_pose, a.skel_type = skel_type;
   a.ref_rel_loc = ref_rel_loc, a.ref_rel_rot = ref_rel_rot, a.ref_abs_rot = ref_abs_rot;
   a.world_loc = world_loc, a.world_rot = world_rot;
   a.rel_rot = relative_pose_rot, a.abs_loc = absolute_pose_loc, a.abs_rot = absolute_pose_rot, a.bones = bones, a.root = root;
   a.N = N, a.frames_per_type = (int32_t)frames_per_type;
-  const int cap = max_blocks > 0 && max_blocks < kMaxBlocks ? max_blocks : kMaxBlocks;
-  const int64_t want = (N + kFramesPerBlock - 1) / kFramesPerBlock;
-  hipLaunchKernelGGL(smpl_to_carla_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(kThreads), 0, (hipStream_t)stream, a);
+  const unsigned grid = p2c_host::grid_for((N + kFramesPerBlock - 1) / kFramesPerBlock, max_blocks, pc::kFrameMaxBlocks);
+  hipLaunchKernelGGL(smpl_to_carla_kernel, dim3(grid), dim3(pc::kFrameThreads), 0, (hipStream_t)stream, a);
   return p2c_host::launch_status();
 }

@@ -158,3 +158,45 @@ def get_projections(device=torch.device('cpu'), as_dict=False, dtype=torch.float
     if as_dict:
         return {k: proj[i] for i, k in enumerate(CARLA_REFERENCE_SKELETON_TYPES)}
     return proj
+
+
+# ---- what the per-frame converters to CARLA poses share (ops.smpl_to_carla / data/smpl/retarget.py, ops.locations_to_carla /
+# walker_control/inverse_kinematics.py): the output keys, the checks behind their own first clause, the type of every frame, the rows
+POSE_KEYS = ('relative_pose_rot', 'absolute_pose_loc', 'absolute_pose_rot')
+ROW_KEYS = ('bones', 'root')
+
+
+def check_shapes(op_name: str, lead, skel_type, world_loc, world_rot, want):
+    """-> ``lead``, the leading dimensions of the converter's input; raises on anything that does not fit them."""
+    if skel_type.is_floating_point() or skel_type.dtype == torch.bool:
+        raise RuntimeError(f'{op_name}: skel_type holds table rows: an integer tensor expected, got {skel_type.dtype}')
+    if not lead or tuple(skel_type.shape) != lead[:skel_type.ndim] or skel_type.ndim < 1:
+        raise RuntimeError(f'{op_name}: skel_type {tuple(skel_type.shape)} is not a prefix of the leading dimensions {lead}')
+    unknown = [k for k in want if k not in POSE_KEYS + ROW_KEYS]
+    if unknown or not want:
+        raise RuntimeError(f'{op_name}: want {tuple(want)}; a non-empty choice of {POSE_KEYS + ROW_KEYS} expected')
+    if (world_loc is None) != (world_rot is None):
+        raise RuntimeError(f'{op_name}: world_loc and world_rot come together or not at all')
+    if world_loc is not None and (tuple(world_loc.shape) != lead + (3,) or tuple(world_rot.shape) != lead + (3, 3)):
+        raise RuntimeError(f'{op_name}: world tensors {tuple(world_loc.shape)}, {tuple(world_rot.shape)}; '
+                           f'{lead + (3,)} and {lead + (3, 3)} expected')
+    if 'root' in want and world_loc is None:
+        raise RuntimeError(f"{op_name}: 'root' needs world_loc and world_rot")
+    return lead
+
+
+def frame_types(skel_type, lead, device=None) -> torch.Tensor:
+    """``skel_type``, its shape a prefix of ``lead`` -> the int64 table row of every frame, (*lead)."""
+    st = skel_type.to(device=device, dtype=torch.long)
+    return st.reshape(tuple(skel_type.shape) + (1,) * (len(lead) - skel_type.ndim)).expand(lead)
+
+
+def carla_rows(want, rel_loc, relative_pose_rot, world_loc, world_rot) -> dict:
+    """The ``want``-ed among ``bones`` / ``root``: the rows of ``ops.carla_pose_export`` on tensor ops, the dtype of the rotations."""
+    from pedestrians_video_2_carla_amd.ops import _carla_row
+    out, dtype = {}, relative_pose_rot.dtype
+    if 'bones' in want:
+        out['bones'] = _carla_row(rel_loc, relative_pose_rot)
+    if 'root' in want:
+        out['root'] = _carla_row(world_loc.to(dtype), world_rot.to(dtype))
+    return out

@@ -25,8 +25,7 @@ from pedestrians_video_2_carla_amd.data.carla.skeleton import CARLA_SKELETON, PA
 from pedestrians_video_2_carla_amd.data.smpl.skeleton import SMPL_SKELETON, map_from_original
 from pedestrians_video_2_carla_amd.transforms.rotation_conversions import euler_angles_to_matrix
 
-POSE_KEYS = ('relative_pose_rot', 'absolute_pose_loc', 'absolute_pose_rot')
-ROW_KEYS = ('bones', 'root')
+POSE_KEYS, ROW_KEYS = ref.POSE_KEYS, ref.ROW_KEYS
 J = len(CARLA_SKELETON)
 
 # CARLA bone j <- SMPL_SKELETON joint SMPL_OF_BONE[j] (-1: the bone keeps the reference pose)
@@ -49,26 +48,7 @@ def check_shapes(body_pose: Tensor, skel_type: Tensor, world_loc: Optional[Tenso
         lead = tuple(body_pose.shape[:-1])
     else:
         raise RuntimeError(f'smpl_to_carla: body_pose (..., 66) or (..., 22, 3) expected, got {tuple(body_pose.shape)}')
-    if skel_type.is_floating_point() or skel_type.dtype == torch.bool:
-        raise RuntimeError(f'smpl_to_carla: skel_type holds table rows: an integer tensor expected, got {skel_type.dtype}')
-    if not lead or tuple(skel_type.shape) != lead[:skel_type.ndim] or skel_type.ndim < 1:
-        raise RuntimeError(f'smpl_to_carla: skel_type {tuple(skel_type.shape)} is not a prefix of the leading dimensions {lead}')
-    unknown = [k for k in want if k not in POSE_KEYS + ROW_KEYS]
-    if unknown or not want:
-        raise RuntimeError(f'smpl_to_carla: want {tuple(want)}; a non-empty choice of {POSE_KEYS + ROW_KEYS} expected')
-    if (world_loc is None) != (world_rot is None):
-        raise RuntimeError('smpl_to_carla: world_loc and world_rot come together or not at all')
-    if world_loc is not None and (tuple(world_loc.shape) != lead + (3,) or tuple(world_rot.shape) != lead + (3, 3)):
-        raise RuntimeError(f'smpl_to_carla: world tensors {tuple(world_loc.shape)}, {tuple(world_rot.shape)}; '
-                           f'{lead + (3,)} and {lead + (3, 3)} expected')
-    if 'root' in want and world_loc is None:
-        raise RuntimeError("smpl_to_carla: 'root' needs world_loc and world_rot")
-    return lead
-
-
-def _carla_row(loc: Tensor, rot: Tensor) -> Tensor:
-    from pedestrians_video_2_carla_amd.ops import _carla_row as row
-    return row(loc, rot)
+    return ref.check_shapes('smpl_to_carla', lead, skel_type, world_loc, world_rot, want)
 
 
 @torch.no_grad()
@@ -87,8 +67,7 @@ def convert_smpl_to_carla(body_pose: Tensor, skel_type: Tensor, world_loc: Optio
     changes[..., _CI, :, :] = m[..., _SI, :, :]
     changes[..., SPINE01, :, :] = m[..., SMPL_SKELETON.Spine3.value, :, :] @ m[..., SMPL_SKELETON.Spine2.value, :, :]
 
-    st = skel_type.to(device=device, dtype=torch.long).reshape(tuple(skel_type.shape) + (1,) * (len(lead) - skel_type.ndim))
-    st = st.expand(lead)
+    st = ref.frame_types(skel_type, lead, device)
     rel_loc, rel_rot = (t[st] for t in ref.get_relative_tensors(device, dtype=dtype))
     _, abs_rot = ref.get_absolute_tensors(device, dtype=dtype)
     local = abs_rot[st] @ conventions_rot(dtype, device)
@@ -113,8 +92,4 @@ def convert_smpl_to_carla(body_pose: Tensor, skel_type: Tensor, world_loc: Optio
             out['absolute_pose_loc'] = torch.stack(a_loc, -2)
         if 'absolute_pose_rot' in want:
             out['absolute_pose_rot'] = torch.stack(a_rot, -3)
-    if 'bones' in want:
-        out['bones'] = _carla_row(rel_loc, relative_pose_rot)
-    if 'root' in want:
-        out['root'] = _carla_row(world_loc.to(dtype), world_rot.to(dtype))
-    return out
+    return {**out, **ref.carla_rows(want, rel_loc, relative_pose_rot, world_loc, world_rot)}

@@ -3406,13 +3406,6 @@ def _lift_chain(changes: Tensor, start: Tensor, exact_fma: bool) -> Tensor:
     return torch.stack(rel, 1)
 
 
-def _lift_world(B, T, world_loc, world_rot, like: Tensor):
-    if world_loc is not None:
-        return world_loc, world_rot
-    return (torch.zeros(B, T, 3, dtype=like.dtype, device=like.device),
-            torch.eye(3, dtype=like.dtype, device=like.device).expand(B, T, 3, 3).contiguous())
-
-
 @torch.no_grad()
 def pose_to_carla_rows(y: Tensor, skel_type: Tensor, kind: str, world_loc: Optional[Tensor] = None,
                        world_rot: Optional[Tensor] = None, initial_rel_rot: Optional[Tensor] = None, want_rot: bool = False,
@@ -3425,7 +3418,7 @@ def pose_to_carla_rows(y: Tensor, skel_type: Tensor, kind: str, world_loc: Optio
     definition on tensor ops (reference projection.py:144-195 and ``carla_pose_export``'s)."""
     B, T = y.shape[:2]
     scan = kind.startswith('pose_changes')
-    wl, wr = _lift_world(B, T, world_loc, world_rot, y)
+    wl, wr = (world_loc, world_rot) if world_loc is not None else identity_world((B, T), y)
     if not tensor_ops and y.is_cuda and y.dtype == torch.float32 and not torch.is_autocast_enabled():
         carry = scan and initial_rel_rot is not None
         want = ('relative_pose_loc', 'relative_pose_rot') + (('pose_changes',) if carry else ())
@@ -3537,10 +3530,45 @@ def _lift_desc(x, weights, biases, skel_type, kind, image, image_is_current, wor
     return d
 
 
-# ---- K35: SMPL body poses (AMASS) -> CARLA bone transforms in one launch (csrc/p2c_smpl.hip) -----------------------------------
-SMPL_CARLA_OUTPUTS = ('relative_pose_rot', 'absolute_pose_loc', 'absolute_pose_rot', 'bones', 'root')
-_SMPL_CARLA_TAIL = {'relative_pose_rot': (J, 3, 3), 'absolute_pose_loc': (J, 3), 'absolute_pose_rot': (J, 3, 3), 'bones': (J, 6),
-                    'root': (6,)}
+# ---- K35, K36: per-frame converters to CARLA poses, one launch each (csrc/p2c_smpl.hip, csrc/p2c_ik.hip) -------------------------
+SMPL_CARLA_OUTPUTS = IK_CARLA_OUTPUTS = ('relative_pose_rot', 'absolute_pose_loc', 'absolute_pose_rot', 'bones', 'root')
+_CARLA_TAIL = {'relative_pose_rot': (J, 3, 3), 'absolute_pose_loc': (J, 3), 'absolute_pose_rot': (J, 3, 3), 'bones': (J, 6),
+               'root': (6,)}
+
+
+def identity_world(lead, like: Tensor) -> Tuple[Tensor, Tensor]:
+    """``world_loc`` (*lead,3) of zeros and ``world_rot`` (*lead,3,3) of identities, dtype and device of ``like``."""
+    lead = tuple(lead)
+    return (torch.zeros(lead + (3,), dtype=like.dtype, device=like.device),
+            torch.eye(3, dtype=like.dtype, device=like.device).expand(lead + (3, 3)).contiguous())
+
+
+def _frames_to_carla(symbol: str, definition, framework: bool, x: Tensor, width: int, lead, skel_type: Tensor, world_loc, world_rot,
+                     want, max_blocks: int, abs_table: bool) -> Dict[str, Tensor]:
+    """What ``smpl_to_carla`` and ``locations_to_carla`` do behind their shape checks: ``x``, ``width`` values in each of its
+    ``lead`` frames, goes to the C-ABI ``symbol`` with the relative reference tables (and the absolute rotations with
+    ``abs_table``) when everything is fp32 on one device outside autocast and ``framework`` is off, else to ``definition``."""
+    floats = [t for t in (x, world_loc, world_rot) if t is not None]
+    if not _carla_kernel_ok(*floats) or framework:
+        return definition(x, skel_type, world_loc, world_rot, want)
+    device = x.device
+    x = x.detach().reshape(lead + (width,)).contiguous()
+    n = x.numel() // width
+    st = skel_type.detach().to(device=device, dtype=torch.int32).contiguous()
+    wl = world_loc.detach().contiguous() if world_loc is not None else None
+    wr = world_rot.detach().contiguous() if world_rot is not None else None
+    frames_per_type = max(n // max(st.numel(), 1), 1)
+    result = {k: torch.empty(lead + _CARLA_TAIL[k], dtype=torch.float32, device=device) for k in SMPL_CARLA_OUTPUTS if k in want}
+    if n == 0:
+        return result
+    tables = [t.data_ptr() for t in ref.get_relative_tensors(device)]
+    if abs_table:
+        tables.append(ref.get_absolute_tensors(device)[1].data_ptr())
+    with torch.cuda.device(device):
+        _lib.check(getattr(_lib.lib(), symbol)(x.data_ptr(), st.data_ptr(), frames_per_type, *tables, _ptr(wl), _ptr(wr),
+                                               *(_ptr(result.get(k)) for k in SMPL_CARLA_OUTPUTS), n, int(max_blocks), _stream()),
+                   symbol)
+    return result
 
 
 def smpl_framework() -> bool:
@@ -3564,33 +3592,8 @@ def smpl_to_carla(body_pose: Tensor, skel_type: Tensor, world_loc: Optional[Tens
     from pedestrians_video_2_carla_amd.data.smpl import retarget
     want = tuple(want)
     lead = retarget.check_shapes(body_pose, skel_type, world_loc, world_rot, want)
-    floats = [t for t in (body_pose, world_loc, world_rot) if t is not None]
-    if not _carla_kernel_ok(*floats) or smpl_framework():
-        return retarget.convert_smpl_to_carla(body_pose, skel_type, world_loc, world_rot, want)
-    lib = _lib.lib()
-    device = body_pose.device
-    pose = body_pose.detach().reshape(lead + (66,)).contiguous()
-    st = skel_type.detach().to(device=device, dtype=torch.int32).contiguous()
-    wl = world_loc.detach().contiguous() if world_loc is not None else None
-    wr = world_rot.detach().contiguous() if world_rot is not None else None
-    n = pose.numel() // 66
-    frames_per_type = max(n // max(st.numel(), 1), 1)
-    result = {k: torch.empty(lead + _SMPL_CARLA_TAIL[k], dtype=torch.float32, device=device)
-              for k in SMPL_CARLA_OUTPUTS if k in want}
-    if n == 0:
-        return result
-    ref_loc, ref_rot = ref.get_relative_tensors(device)
-    _, ref_abs = ref.get_absolute_tensors(device)
-    with torch.cuda.device(device):
-        _lib.check(lib.p2c_smpl_to_carla_fwd(pose.data_ptr(), st.data_ptr(), frames_per_type, ref_loc.data_ptr(),
-                                             ref_rot.data_ptr(), ref_abs.data_ptr(), _ptr(wl), _ptr(wr),
-                                             *(_ptr(result.get(k)) for k in SMPL_CARLA_OUTPUTS), n, int(max_blocks), _stream()),
-                   'p2c_smpl_to_carla_fwd')
-    return result
-
-
-# ---- K36: 3-D joint locations -> CARLA bone rotations, inverse kinematics in one launch (csrc/p2c_ik.hip) ----------------------
-IK_CARLA_OUTPUTS = ('relative_pose_rot', 'absolute_pose_loc', 'absolute_pose_rot', 'bones', 'root')
+    return _frames_to_carla('p2c_smpl_to_carla_fwd', retarget.convert_smpl_to_carla, smpl_framework(), body_pose, 66, lead,
+                            skel_type, world_loc, world_rot, want, max_blocks, abs_table=True)
 
 
 def ik_framework() -> bool:
@@ -3615,28 +3618,8 @@ def locations_to_carla(loc: Tensor, skel_type: Tensor, world_loc: Optional[Tenso
     from pedestrians_video_2_carla_amd.walker_control import inverse_kinematics as ik
     want = tuple(want)
     lead = ik.check_shapes(loc, skel_type, world_loc, world_rot, want)
-    floats = [t for t in (loc, world_loc, world_rot) if t is not None]
-    if not _carla_kernel_ok(*floats) or ik_framework():
-        return ik.fit_carla_rotations(loc, skel_type, world_loc, world_rot, want)
-    lib = _lib.lib()
-    device = loc.device
-    x = loc.detach().contiguous()
-    st = skel_type.detach().to(device=device, dtype=torch.int32).contiguous()
-    wl = world_loc.detach().contiguous() if world_loc is not None else None
-    wr = world_rot.detach().contiguous() if world_rot is not None else None
-    n = x.numel() // (J * 3)
-    frames_per_type = max(n // max(st.numel(), 1), 1)
-    result = {k: torch.empty(lead + _SMPL_CARLA_TAIL[k], dtype=torch.float32, device=device)
-              for k in IK_CARLA_OUTPUTS if k in want}
-    if n == 0:
-        return result
-    ref_loc, ref_rot = ref.get_relative_tensors(device)
-    with torch.cuda.device(device):
-        _lib.check(lib.p2c_loc_to_carla_fwd(x.data_ptr(), st.data_ptr(), frames_per_type, ref_loc.data_ptr(), ref_rot.data_ptr(),
-                                            _ptr(wl), _ptr(wr), *(_ptr(result.get(k)) for k in IK_CARLA_OUTPUTS), n,
-                                            int(max_blocks), _stream()),
-                   'p2c_loc_to_carla_fwd')
-    return result
+    return _frames_to_carla('p2c_loc_to_carla_fwd', ik.fit_carla_rotations, ik_framework(), loc, J * 3, lead, skel_type,
+                            world_loc, world_rot, want, max_blocks, abs_table=False)
 
 
 # ---- K33: decoded video clips -> the pose-estimation flow's input frames (csrc/p2c_frames.hip) ---------------------------------

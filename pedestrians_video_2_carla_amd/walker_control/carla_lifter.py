@@ -14,9 +14,9 @@ import torch
 from torch import Tensor
 
 from pedestrians_video_2_carla_amd import ops
-from pedestrians_video_2_carla_amd.data.carla import reference as ref
 from pedestrians_video_2_carla_amd.modules.flow.output_types import MovementsModelOutputType
 from pedestrians_video_2_carla_amd.modules.movements.linear_ae import LinearAE
+from pedestrians_video_2_carla_amd.walker_control.carla_pose import skel_type_of
 
 _KINDS = {MovementsModelOutputType.pose_changes: 'pose_changes', MovementsModelOutputType.relative_rot: 'relative_rot'}
 
@@ -104,11 +104,6 @@ class CarlaLifter:
         self._carry = None
 
     # ---- the work ----------------------------------------------------------------------------------------------------
-    def _skel_type(self, meta_or_skel_type, B: int, device) -> Tensor:
-        if isinstance(meta_or_skel_type, Tensor):
-            return meta_or_skel_type.to(device=device, dtype=torch.int32)
-        return ref.skeleton_types_from_meta(meta_or_skel_type, batch_size=B, strict=True, device=device)
-
     @torch.no_grad()
     def _run(self, frames, meta_or_skel_type, world_loc, world_rot, initial):
         if self.device is not None:
@@ -120,7 +115,7 @@ class CarlaLifter:
         B = frames.shape[0]
         if initial is not None and initial.shape[0] != B:
             raise RuntimeError(f'CarlaLifter.push: {B} clips after {initial.shape[0]}; reset() starts another video')
-        skel_type = self._skel_type(meta_or_skel_type, B, frames.device)
+        skel_type = skel_type_of(meta_or_skel_type, B, frames.device, strict=True)
         plan = self._linear_ae()
         if plan is not None:
             weights, biases, dims = plan

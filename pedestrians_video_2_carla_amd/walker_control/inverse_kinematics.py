@@ -39,8 +39,7 @@ from torch import Tensor
 from pedestrians_video_2_carla_amd.data.carla import reference as ref
 from pedestrians_video_2_carla_amd.data.carla.skeleton import CARLA_SKELETON, PARENTS
 
-POSE_KEYS = ('relative_pose_rot', 'absolute_pose_loc', 'absolute_pose_rot')
-ROW_KEYS = ('bones', 'root')
+POSE_KEYS, ROW_KEYS = ref.POSE_KEYS, ref.ROW_KEYS
 J = len(CARLA_SKELETON)
 CHILDREN = tuple(tuple(c for c, p in enumerate(PARENTS) if p == j) for j in range(J))
 ANTIPARALLEL_EPS = 2.0 ** -40          # |u + v|^2 at or below which the shortest arc is the half turn
@@ -48,33 +47,12 @@ ANTIPARALLEL_EPS = 2.0 ** -40          # |u + v|^2 at or below which the shortes
 
 def check_shapes(loc: Tensor, skel_type: Tensor, world_loc: Optional[Tensor], world_rot: Optional[Tensor],
                  want: Sequence[str]):
-    """-> the leading dimensions of ``loc`` (..., 26, 3); raises on anything that does not fit them (the checks of
-    ``data/smpl/retarget.check_shapes``)."""
+    """-> the leading dimensions of ``loc`` (..., 26, 3); raises on anything that does not fit them."""
     if loc.ndim < 2 or tuple(loc.shape[-2:]) != (J, 3):
         raise RuntimeError(f'locations_to_carla: loc (..., {J}, 3) expected, got {tuple(loc.shape)}')
     if not loc.is_floating_point():
         raise RuntimeError(f'locations_to_carla: loc holds coordinates: a floating tensor expected, got {loc.dtype}')
-    lead = tuple(loc.shape[:-2])
-    if skel_type.is_floating_point() or skel_type.dtype == torch.bool:
-        raise RuntimeError(f'locations_to_carla: skel_type holds table rows: an integer tensor expected, got {skel_type.dtype}')
-    if not lead or tuple(skel_type.shape) != lead[:skel_type.ndim] or skel_type.ndim < 1:
-        raise RuntimeError(f'locations_to_carla: skel_type {tuple(skel_type.shape)} is not a prefix of the leading dimensions {lead}')
-    unknown = [k for k in want if k not in POSE_KEYS + ROW_KEYS]
-    if unknown or not want:
-        raise RuntimeError(f'locations_to_carla: want {tuple(want)}; a non-empty choice of {POSE_KEYS + ROW_KEYS} expected')
-    if (world_loc is None) != (world_rot is None):
-        raise RuntimeError('locations_to_carla: world_loc and world_rot come together or not at all')
-    if world_loc is not None and (tuple(world_loc.shape) != lead + (3,) or tuple(world_rot.shape) != lead + (3, 3)):
-        raise RuntimeError(f'locations_to_carla: world tensors {tuple(world_loc.shape)}, {tuple(world_rot.shape)}; '
-                           f'{lead + (3,)} and {lead + (3, 3)} expected')
-    if 'root' in want and world_loc is None:
-        raise RuntimeError("locations_to_carla: 'root' needs world_loc and world_rot")
-    return lead
-
-
-def _carla_row(loc: Tensor, rot: Tensor) -> Tensor:
-    from pedestrians_video_2_carla_amd.ops import _carla_row as row
-    return row(loc, rot)
+    return ref.check_shapes('locations_to_carla', tuple(loc.shape[:-2]), skel_type, world_loc, world_rot, want)
 
 
 def quaternion_rows(q0: Tensor, qx: Tensor, qy: Tensor, qz: Tensor) -> Tensor:
@@ -132,8 +110,7 @@ def fit_carla_rotations(loc: Tensor, skel_type: Tensor, world_loc: Optional[Tens
     want = tuple(want)
     lead = check_shapes(loc, skel_type, world_loc, world_rot, want)
     dtype, device = loc.dtype, loc.device
-    st = skel_type.to(device=device, dtype=torch.long).reshape(tuple(skel_type.shape) + (1,) * (len(lead) - skel_type.ndim))
-    st = st.expand(lead)
+    st = ref.frame_types(skel_type, lead, device)
     rel_loc, ref_rot = (t[st] for t in ref.get_relative_tensors(device, dtype=dtype))
 
     A, rel, a_loc = [None] * J, [None] * J, [None] * J
@@ -175,8 +152,4 @@ def fit_carla_rotations(loc: Tensor, skel_type: Tensor, world_loc: Optional[Tens
         out['absolute_pose_loc'] = torch.stack(a_loc, -2)
     if 'absolute_pose_rot' in want:
         out['absolute_pose_rot'] = torch.stack(A, -3)
-    if 'bones' in want:
-        out['bones'] = _carla_row(rel_loc, relative_pose_rot)
-    if 'root' in want:
-        out['root'] = _carla_row(world_loc.to(dtype), world_rot.to(dtype))
-    return out
+    return {**out, **ref.carla_rows(want, rel_loc, relative_pose_rot, world_loc, world_rot)}

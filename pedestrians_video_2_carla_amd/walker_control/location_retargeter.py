@@ -17,22 +17,15 @@ import torch
 from torch import Tensor
 
 from pedestrians_video_2_carla_amd import ops
-from pedestrians_video_2_carla_amd.data.carla import reference as ref
 from pedestrians_video_2_carla_amd.data.carla.skeleton import CARLA_SKELETON
 from pedestrians_video_2_carla_amd.modules.flow.output_types import MovementsModelOutputType
+from pedestrians_video_2_carla_amd.walker_control.carla_pose import Retargeter, skel_type_of
 
 _LOCATION_OUTPUTS = (MovementsModelOutputType.absolute_loc, MovementsModelOutputType.absolute_loc_rot)
 
 
-class LocationRetargeter:
-    def __init__(self, device=None):
-        self.device = torch.device(device) if device is not None else None
-
-    def _skel_type(self, meta_or_skel_type, B: int, device) -> Tensor:
-        """(age, gender) through the de-normaliser's substitutions, as ``SmplRetargeter`` reads them."""
-        if isinstance(meta_or_skel_type, Tensor):
-            return meta_or_skel_type.to(device=device, dtype=torch.int32)
-        return ref.skeleton_types_from_meta(meta_or_skel_type, batch_size=B, strict=False, device=device)
+class LocationRetargeter(Retargeter):
+    _op = 'locations_to_carla'
 
     def _inputs(self, loc_or_sliced, meta_or_skel_type, world_loc: Optional[Tensor], world_rot: Optional[Tensor]):
         if isinstance(loc_or_sliced, (tuple, list)):                  # (sliced, meta) as predict_step returns it
@@ -60,13 +53,11 @@ class LocationRetargeter:
         if loc.ndim < 3 or tuple(loc.shape[-2:]) != (len(CARLA_SKELETON), 3):
             raise RuntimeError(f'LocationRetargeter: locations (B,...,26,3) in CARLA_SKELETON order expected, got {tuple(loc.shape)}')
         lead = tuple(loc.shape[:-2])
-        skel_type = self._skel_type(meta_or_skel_type, lead[0], loc.device)
-        e = dict(dtype=loc.dtype, device=loc.device)
+        skel_type = skel_type_of(meta_or_skel_type, lead[0], loc.device, strict=False)
         if world_loc is None:
-            world_loc = torch.zeros(lead + (3,), **e)
-            world_rot = torch.eye(3, **e).expand(lead + (3, 3)).contiguous()
+            world_loc, world_rot = ops.identity_world(lead, loc)
         else:
-            world_loc, world_rot = world_loc.to(**e), world_rot.to(**e)
+            world_loc, world_rot = (t.to(dtype=loc.dtype, device=loc.device) for t in (world_loc, world_rot))
         return loc, skel_type, world_loc, world_rot, lead
 
     @torch.no_grad()
@@ -76,19 +67,13 @@ class LocationRetargeter:
         tensors are then used -- and the batch's ``meta`` ('age' / 'gender' lists or 'skel_type') or a (B) skeleton-type tensor ->
         ``relative_pose_loc`` (the reference rows), ``relative_pose_rot``, ``absolute_pose_loc`` (re-targeted to the reference
         bone lengths), ``absolute_pose_rot``, ``world_loc`` and ``world_rot`` (zeros and the identity when none were given)."""
-        loc, skel_type, world_loc, world_rot, lead = self._inputs(loc_or_sliced, meta_or_skel_type, world_loc, world_rot)
-        out = ops.locations_to_carla(loc, skel_type)
-        ref_loc, _ = ref.get_relative_tensors(loc.device, dtype=loc.dtype)
-        st = skel_type.long().reshape(tuple(skel_type.shape) + (1,) * (len(lead) - skel_type.ndim)).expand(lead)
-        return {'relative_pose_loc': ref_loc[st], **out, 'world_loc': world_loc, 'world_rot': world_rot}
+        return self._retarget(*self._inputs(loc_or_sliced, meta_or_skel_type, world_loc, world_rot))
 
     @torch.no_grad()
     def export(self, loc_or_sliced, meta_or_skel_type=None, world_loc: Optional[Tensor] = None,
                world_rot: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
         """The rows of ``export_clips(self.retarget(...))`` without the pose tensors: ``bones`` (...,26,6), ``root`` (...,6)."""
-        loc, skel_type, world_loc, world_rot, _ = self._inputs(loc_or_sliced, meta_or_skel_type, world_loc, world_rot)
-        out = ops.locations_to_carla(loc, skel_type, world_loc, world_rot, want=('bones', 'root'))
-        return out['bones'], out['root']
+        return self._export(*self._inputs(loc_or_sliced, meta_or_skel_type, world_loc, world_rot))
 
     @staticmethod
     def check_flow(flow) -> None:

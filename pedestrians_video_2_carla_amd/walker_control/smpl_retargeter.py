@@ -12,19 +12,11 @@ import torch
 from torch import Tensor
 
 from pedestrians_video_2_carla_amd import ops
-from pedestrians_video_2_carla_amd.data.carla import reference as ref
+from pedestrians_video_2_carla_amd.walker_control.carla_pose import Retargeter, skel_type_of
 
 
-class SmplRetargeter:
-    def __init__(self, device=None):
-        self.device = torch.device(device) if device is not None else None
-
-    def _skel_type(self, meta_or_skel_type, B: int, device) -> Tensor:
-        """(age, gender) through the de-normaliser's substitutions: ``neutral`` and missing values are the adult female skeleton,
-        as the reference warns (smpl_dataset.py:31-33)."""
-        if isinstance(meta_or_skel_type, Tensor):
-            return meta_or_skel_type.to(device=device, dtype=torch.int32)
-        return ref.skeleton_types_from_meta(meta_or_skel_type, batch_size=B, strict=False, device=device)
+class SmplRetargeter(Retargeter):
+    _op = 'smpl_to_carla'
 
     def _inputs(self, body_pose: Tensor, meta_or_skel_type, world_rot: Optional[Tensor]):
         if self.device is not None:
@@ -35,13 +27,12 @@ class SmplRetargeter:
         lead = tuple(body_pose.shape[:-2] if tuple(body_pose.shape[-2:]) == (22, 3) else body_pose.shape[:-1])
         if not lead:
             raise RuntimeError(f'SmplRetargeter: body_pose (B,...,66) or (B,...,22,3) expected, got {tuple(body_pose.shape)}')
-        skel_type = self._skel_type(meta_or_skel_type, lead[0], body_pose.device)
-        e = dict(dtype=body_pose.dtype, device=body_pose.device)
-        world_loc = torch.zeros(lead + (3,), **e)
+        skel_type = skel_type_of(meta_or_skel_type, lead[0], body_pose.device, strict=False)
         if world_rot is None:
-            world_rot = torch.eye(3, **e).expand(lead + (3, 3)).contiguous()
+            world_loc, world_rot = ops.identity_world(lead, body_pose)
         else:
-            world_rot = world_rot.to(**e)
+            e = dict(dtype=body_pose.dtype, device=body_pose.device)
+            world_loc, world_rot = torch.zeros(lead + (3,), **e), world_rot.to(**e)
         return body_pose, skel_type, world_loc, world_rot, lead
 
     @torch.no_grad()
@@ -49,15 +40,9 @@ class SmplRetargeter:
         """``body_pose`` (B,T,66) / (B,T,22,3) (or without T), the batch's ``meta`` ('age' / 'gender' lists or 'skel_type') or a
         (B) skeleton-type tensor, ``world_rot`` (B,T,3,3) or None (identity) -> ``relative_pose_loc`` (the reference rows),
         ``relative_pose_rot``, ``absolute_pose_loc``, ``absolute_pose_rot``, ``world_loc`` (zeros) and ``world_rot``."""
-        pose, skel_type, world_loc, world_rot, lead = self._inputs(body_pose, meta_or_skel_type, world_rot)
-        out = ops.smpl_to_carla(pose, skel_type)
-        ref_loc, _ = ref.get_relative_tensors(pose.device, dtype=pose.dtype)
-        st = skel_type.long().reshape(tuple(skel_type.shape) + (1,) * (len(lead) - skel_type.ndim)).expand(lead)
-        return {'relative_pose_loc': ref_loc[st], **out, 'world_loc': world_loc, 'world_rot': world_rot}
+        return self._retarget(*self._inputs(body_pose, meta_or_skel_type, world_rot))
 
     @torch.no_grad()
     def export(self, body_pose: Tensor, meta_or_skel_type, world_rot: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
         """The rows of ``export_clips(self.retarget(...))`` without the pose tensors: ``bones`` (...,26,6), ``root`` (...,6)."""
-        pose, skel_type, world_loc, world_rot, _ = self._inputs(body_pose, meta_or_skel_type, world_rot)
-        out = ops.smpl_to_carla(pose, skel_type, world_loc, world_rot, want=('bones', 'root'))
-        return out['bones'], out['root']
+        return self._export(*self._inputs(body_pose, meta_or_skel_type, world_rot))

@@ -20,11 +20,11 @@ from pedestrians_video_2_carla_amd.data.carla import reference as ref
 from pedestrians_video_2_carla_amd.data.carla.skeleton import CARLA_SKELETON
 from pedestrians_video_2_carla_amd.walker_control import inverse_kinematics as ik
 from test_ik import POSE_KEYS, fixture, nan_joint_cases, round_trip, truth
+from test_smpl_retarget_gpu import TAIL, dev, same_bits      # the two converters have the same outputs
 
 pytestmark = pytest.mark.gpu
 
 ALL = ops.IK_CARLA_OUTPUTS
-TAIL = {'relative_pose_rot': (26, 3, 3), 'absolute_pose_loc': (26, 3), 'absolute_pose_rot': (26, 3, 3), 'bones': (26, 6), 'root': (6,)}
 
 
 def frames_per_wavefront(N):
@@ -36,11 +36,6 @@ F, G = frames_per_wavefront(1), 4 * frames_per_wavefront(1)
 # N at which the kernel takes larger chunks: p = 2 (F = 4, G = 16: 2049 = 512 F + 1, 2051 = 512 F + 3, 2063 / 2064 / 2065 = 129 G - 1,
 # 129 G, 129 G + 1) and p = 10 (F = 20, G = 80: 18433 = 921 F + 13 = 230 G + 33, 18480 = 231 G)
 CHUNKED = [2049, 2051, 2063, 2064, 2065, 18433, 18480]
-
-
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
 
 
 @functools.lru_cache(maxsize=None)
@@ -65,10 +60,6 @@ def run_all(N, max_blocks=0):
 def baseline(N):
     """The all-outputs call at the kernel's own grid, on the host: what every other regime must reproduce bit for bit."""
     return {k: v.cpu() for k, v in run_all(N).items()}
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.cpu().view(torch.int32), b.cpu().view(torch.int32))
 
 
 def within_bound(got, t64, what):
