@@ -1157,6 +1157,32 @@ P2C_API int p2c_loc_to_carla_fwd(const float *loc, const int32_t *skel_type, int
                                  float *relative_pose_rot, float *absolute_pose_loc, float *absolute_pose_rot, float *bones,
                                  float *root, int64_t N, int32_t max_blocks, void *stream);
 
+/* ---- K37: CARLA rows resampled to another frame rate in one launch (csrc/p2c_resample.hip) -----------------------------------
+ * What lets rows exported at a source's rate (video 30 / 29.97 fps, mocap 60 / 120 fps) be played at the simulator's tick; the
+ * reference has no such step. Definition: walker_control/resample.py. N videos, each row (x, y, z, pitch, yaw, roll).
+ *   bones (N,T,J,6), root (N,T,6) or NULL: the source frames with global indices first_frame .. first_frame + T - 1.
+ *   carry_bones (N,J,6), carry_root (N,6) or NULL: the source frame with global index first_frame - 1 (a streaming caller's
+ *     last frame of the previous chunk).
+ *   out_bones (N,K,J,6), out_root (N,K,6) or NULL: output samples with global indices first_output .. first_output + K - 1.
+ * Output sample k sits at source position p = fl64(k * ratio), ratio = src_fps / dst_fps: i0 = floor(p), frac = (float)(p - i0).
+ * mode P2C_RESAMPLE_SLERP: frac == 0 copies row i0 bit for bit (row i0 + 1 is not read); otherwise locations are
+ * a + frac (b - a) and rotations the shortest-arc spherical interpolation of the rows' quaternions (w first, q = qx(e0) qy(e1)
+ * qz(e2), (e0, e1, e2) = radians(-roll, -pitch, -yaw); weights (1 - frac, frac) above a dot product of 0.99999), written back
+ * through the row arithmetic of p2c_carla_pose_fwd. mode P2C_RESAMPLE_HOLD: row i0, copied. A NaN in a neighbour reaches that
+ * output row and nothing else. A source index outside [first_frame - (carry given), first_frame + T - 1] is clamped in the
+ * kernel, never followed: the caller checks that the requested outputs lie inside.
+ * max_blocks  0: the kernel's own grid cap; > 0 lowers it (lanes stride over the output rows).
+ * One lane per output row, one writer per element, nothing reduced; a row's bits depend on its two source rows and frac only.
+ * In this order, before anything is launched: P2C_E_SHAPE for negative sizes or indices, J < 1, max_blocks < 0, N K (J + 1) > 2^40,
+ * N T (J + 1) > 2^40, first_frame + T or first_output + K > 2^40, ratio not finite or outside [2^-10, 2^10], another mode, outputs
+ * asked of no frames (T = 0 with N, K > 0); P2C_E_NULL for a missing bones / out_bones, root without out_root or the reverse,
+ * carry_root without carry_bones, carry_bones without carry_root when root is given. Then N = 0 or K = 0: nothing is launched. */
+enum { P2C_RESAMPLE_SLERP = 0, P2C_RESAMPLE_HOLD = 1 };
+P2C_API int p2c_carla_resample_fwd(const float *bones, const float *root, const float *carry_bones, const float *carry_root,
+                                   float *out_bones, float *out_root, int64_t N, int64_t T, int32_t J, int64_t K,
+                                   int64_t first_output, int64_t first_frame, double ratio, int32_t mode, int32_t max_blocks,
+                                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -367,6 +367,7 @@ SYMBOLS = {
     'p2c_render_points_fwd': (ctypes.c_int, [ctypes.POINTER(RenderPointsDesc), _vp]),
     'p2c_smpl_to_carla_fwd': (ctypes.c_int, [_vp, _vp, _i64] + [_vp] * 10 + [_i64, _i32, _vp]),
     'p2c_loc_to_carla_fwd': (ctypes.c_int, [_vp, _vp, _i64] + [_vp] * 9 + [_i64, _i32, _vp]),
+    'p2c_carla_resample_fwd': (ctypes.c_int, [_vp] * 6 + [_i64, _i64, _i32, _i64, _i64, _i64, ctypes.c_double, _i32, _i32, _vp]),
 }
 
 _lib = None

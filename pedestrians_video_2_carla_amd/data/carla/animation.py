@@ -2,7 +2,8 @@
 
 One ``.npz`` with ``bones`` (N,T,J,6) and ``root`` (N,T,6) -- rows of (x, y, z, pitch, yaw, roll), metres and degrees, CARLA's
 axes, see ``ops.carla_pose_export`` -- ``bone_names`` (J), ``age`` / ``gender`` (N: which walker blueprint a clip belongs to)
-and ``fps``. Playing it needs a CARLA server and is not part of this package. Four writers, one file format: predictions
+and ``fps``. Playing it needs a CARLA server and is not part of this package. ``resample_carla_animation`` rewrites a file at
+another rate (K37). Four writers, one file format: predictions
 (``save_carla_animation``), keypoint clips through a LinearAE flow (``lift_carla_animation``, K32), mocap clips
 (``retarget_carla_animation``, K35) and keypoint clips through a flow that predicts 3-D locations (``ik_carla_animation``, K36).
 """
@@ -13,30 +14,41 @@ import numpy as np
 from pedestrians_video_2_carla_amd.walker_control.carla_pose import BONE_NAMES, export_clips
 
 
-def save_carla_animation(path: str, outputs, fps: float = 30.0) -> str:
+def save_carla_animation(path: str, outputs, fps: float = 30.0, out_fps=None) -> str:
     """``outputs``: the list ``Trainer.predict`` returns, ``(sliced, meta)`` per batch. Every batch is converted with one
-    ``carla_pose_export`` call and copied to the host once. Returns the path written (``.npz`` appended when missing)."""
+    ``carla_pose_export`` call and copied to the host once. Returns the path written (``.npz`` appended when missing).
+    ``out_fps`` (here and in the other writers): every clip is resampled from ``fps`` to that rate where its rows are, before the
+    copy (``ops.resample_carla_rows``, K37 on the device), and the file's ``fps`` is ``out_fps``."""
     outputs = list(outputs)
     if not outputs:
         raise ValueError('no predictions to save')
+    resample = _resampler(fps, out_fps)
     rows = []
     for sliced, meta in outputs:
-        b, r = export_clips(sliced)
+        b, r = export_clips(sliced, resample)
         if r is None:
             raise KeyError('world_loc / world_rot are missing from the predictions: no root transform to store')
         rows.append((b, r, meta))
-    return _write(path, rows, fps)
+    return _write(path, rows, fps if out_fps is None else out_fps)
 
 
-def lift_carla_animation(path: str, flow, batches, fps: float = 30.0) -> str:
+def _resampler(fps, out_fps):
+    """None without ``out_fps``, else ``(bones, root) -> (bones, root)`` at ``out_fps``: stateless, every clip its own video."""
+    if out_fps is None:
+        return None
+    from pedestrians_video_2_carla_amd.walker_control.resample import CarlaResampler
+    return CarlaResampler(fps, out_fps).resample
+
+
+def lift_carla_animation(path: str, flow, batches, fps: float = 30.0, out_fps=None) -> str:
     """The file ``save_carla_animation(path, trainer.predict(flow, batches), fps)`` writes, from ``Trainer.predict_carla``:
     a LinearAE flow takes one launch per batch (K32) and no pose tensor is materialised; bones and root travel to the host
     together, one copy per batch. ``batches``: ``(frames, targets, meta)`` as for ``predict``."""
     from pedestrians_video_2_carla_amd.trainer import Trainer
-    return _write_device_rows(path, Trainer().predict_carla(flow, batches), fps, 'no predictions to save')
+    return _write_device_rows(path, Trainer().predict_carla(flow, batches), fps, 'no predictions to save', out_fps)
 
 
-def retarget_carla_animation(path: str, batches, fps: float = 30.0, device=None) -> str:
+def retarget_carla_animation(path: str, batches, fps: float = 30.0, device=None, out_fps=None) -> str:
     """Mocap clips as the file ``save_carla_animation`` writes: ``batches`` of ``(frames, targets, meta)`` whose targets hold
     ``amass_body_pose`` (B,T,66) -- the stored AMASS subsets, a mixture's AMASS clips -- and ``world_rot`` (B,T,3,3) where the
     subset has it (the identity otherwise; the root location of a body pose is zero). One ``ops.smpl_to_carla`` call per batch
@@ -49,29 +61,32 @@ def retarget_carla_animation(path: str, batches, fps: float = 30.0, device=None)
             if 'amass_body_pose' not in targets:
                 raise KeyError('amass_body_pose is missing from the targets: not a batch of AMASS clips')
             yield (*retargeter.export(targets['amass_body_pose'], meta, targets.get('world_rot')), meta)
-    return _write_device_rows(path, clips(), fps, 'no clips to save')
+    return _write_device_rows(path, clips(), fps, 'no clips to save', out_fps)
 
 
-def ik_carla_animation(path: str, flow, batches, fps: float = 30.0) -> str:
+def ik_carla_animation(path: str, flow, batches, fps: float = 30.0, out_fps=None) -> str:
     """The file of ``save_carla_animation`` from a flow whose movements model outputs absolute locations (PoseFormer,
     Baseline3DPose, ``--movements_output_type absolute_loc``): ``Trainer.predict_carla(flow, batches, ik=True)`` fits the bone
     rotations to the predicted locations with one launch of K36 per batch; bones and root travel to the host together, one copy
     per batch. ``batches``: ``(frames, targets, meta)`` as for ``predict``."""
     from pedestrians_video_2_carla_amd.trainer import Trainer
-    return _write_device_rows(path, Trainer().predict_carla(flow, batches, ik=True), fps, 'no predictions to save')
+    return _write_device_rows(path, Trainer().predict_carla(flow, batches, ik=True), fps, 'no predictions to save', out_fps)
 
 
-def _write_device_rows(path: str, batches, fps: float, when_empty: str) -> str:
+def _write_device_rows(path: str, batches, fps: float, when_empty: str, out_fps=None) -> str:
     """``batches`` of (bones (n,T,J,6), root (n,T,6), meta) on the device: bones and root travel to the host together, one copy
-    per batch."""
+    per batch, resampled to ``out_fps`` before it when that is given."""
     import torch
+    resample = _resampler(fps, out_fps)
     rows = []
     for bones, root, meta in batches:
+        if resample is not None:
+            bones, root = resample(bones, root)
         both = torch.cat((bones, root.unsqueeze(-2)), -2).cpu().numpy()
         rows.append((both[..., :-1, :], both[..., -1, :], meta))
     if not rows:
         raise ValueError(when_empty)
-    return _write(path, rows, fps)
+    return _write(path, rows, fps if out_fps is None else out_fps)
 
 
 def _write(path: str, rows, fps: float) -> str:
@@ -91,6 +106,26 @@ def _write(path: str, rows, fps: float) -> str:
     np.savez(path, bones=bones.astype(np.float32), root=roots.astype(np.float32), bone_names=np.array(BONE_NAMES),
              age=np.array(ages), gender=np.array(genders), fps=np.float64(fps))
     return str(path)
+
+
+def resample_carla_animation(src_path: str, dst_path: str, fps: float, mode: str = 'slerp', device=None, chunk=None) -> str:
+    """The file at ``src_path`` at ``fps`` frames per second: every clip resampled from the stored rate (``CarlaResampler``; on
+    ``device``, K37 there for a GPU), everything else as stored. ``chunk``: the clips stream through ``push`` in pieces of that
+    many frames, as a video that arrives clip by clip would. Returns the path written."""
+    import torch
+    from pedestrians_video_2_carla_amd.walker_control.resample import CarlaResampler
+    src = load_carla_animation(src_path)
+    resampler = CarlaResampler(src['fps'], fps, mode)
+    bones, root = (torch.from_numpy(src[k]).to(device) if device is not None else torch.from_numpy(src[k]) for k in ('bones', 'root'))
+    if chunk is None:
+        out_b, out_r = resampler.resample(bones, root)
+    else:
+        if int(chunk) < 1:
+            raise ValueError(f'resample_carla_animation: chunk = {chunk}; at least one frame expected')
+        pieces = [resampler.push(bones[:, t:t + int(chunk)], root[:, t:t + int(chunk)]) for t in range(0, bones.shape[1], int(chunk))]
+        out_b, out_r = torch.cat([p[0] for p in pieces], 1), torch.cat([p[1] for p in pieces], 1)
+    both = torch.cat((out_b, out_r.unsqueeze(-2)), -2).cpu().numpy()
+    return _write(dst_path, [(both[..., :-1, :], both[..., -1, :], {'age': src['age'], 'gender': src['gender']})], fps)
 
 
 def load_carla_animation(path: str) -> Dict[str, object]:

@@ -3622,6 +3622,54 @@ def locations_to_carla(loc: Tensor, skel_type: Tensor, world_loc: Optional[Tenso
                             world_loc, world_rot, want, max_blocks, abs_table=False)
 
 
+# ---- K37: CARLA rows resampled to another frame rate (csrc/p2c_resample.hip) ---------------------------------------------------
+def resample_framework() -> bool:
+    """P2C_RESAMPLE_FRAMEWORK=1: ``resample_carla_rows`` runs its tensor definition on the device (the comparison arm of
+    tools/bench_resample.py)."""
+    return os.environ.get('P2C_RESAMPLE_FRAMEWORK', '0') == '1'
+
+
+@torch.no_grad()
+def resample_carla_rows(bones: Tensor, root: Optional[Tensor] = None, *, src_fps, dst_fps, mode: str = 'slerp', carry=None,
+                        first_frame: int = 0, first_output: int = 0, count: Optional[int] = None,
+                        max_blocks: int = 0) -> Tuple[Tensor, Optional[Tensor]]:
+    """Exported rows at the rate of a simulator's tick (definition: ``walker_control/resample.py``). ``bones`` (N,T,J,6) and
+    ``root`` (N,T,6) or None, rows of (x, y, z, pitch, yaw, roll) at ``src_fps`` -> ``(bones (N,K,J,6), root (N,K,6) or None)`` at
+    ``dst_fps``: output ``k`` sits at source position ``fl64(k * (src_fps / dst_fps))``; where that is a whole number the source
+    row is copied bit for bit, elsewhere ``mode='slerp'`` interpolates locations linearly and rotations along the shortest arc
+    and ``mode='hold'`` copies the row before. ``bones[:, 0]`` is global source frame ``first_frame``, ``out[:, 0]`` global output
+    ``first_output``; ``count`` outputs are returned (None: all up to the last frame given); ``carry`` = ``(bones (N,J,6),
+    root (N,6) or None)`` is source frame ``first_frame - 1`` (``CarlaResampler.push`` keeps it). Outputs that read a frame that
+    is not given raise. Any J >= 1; views are made contiguous; nothing is recorded for autograd. fp32 device tensors outside
+    autocast take K37 (one launch for bones and root); host tensors, fp64, other dtypes and ``P2C_RESAMPLE_FRAMEWORK=1`` take the
+    tensor definition. ``max_blocks`` lowers the kernel's grid cap (tests)."""
+    from pedestrians_video_2_carla_amd.walker_control import resample as rs
+    ratio = rs.rate_ratio(src_fps, dst_fps)
+    mode_id = rs.check_mode(mode)
+    first_frame, first_output = int(first_frame), int(first_output)
+    cb, cr = rs.check_rows(bones, root, carry)
+    N, T, n_joints, _ = bones.shape
+    if count is None:
+        count = max(rs.output_count(first_frame + T - 1, ratio) - first_output, 0)
+    count = int(count)
+    if first_frame == 0:                       # nothing lies before the first frame of a video
+        cb = cr = None
+    rs.check_span(first_output, count, ratio, first_frame, T, cb is not None, 'resample_carla_rows')
+    given = [t for t in (bones, root, cb, cr) if t is not None]
+    if not _carla_kernel_ok(*given) or resample_framework():
+        return rs.resample_rows(bones, root, cb, cr, ratio, mode_id == rs.MODES['hold'], first_frame, first_output, count)
+    src_b, src_r, cb, cr = (t.detach().contiguous() if t is not None else None for t in (bones, root, cb, cr))
+    out_b = torch.empty((N, count, n_joints, 6), dtype=torch.float32, device=bones.device)
+    out_r = torch.empty((N, count, 6), dtype=torch.float32, device=bones.device) if root is not None else None
+    if N == 0 or count == 0:
+        return out_b, out_r
+    with torch.cuda.device(bones.device):
+        _lib.check(_lib.lib().p2c_carla_resample_fwd(src_b.data_ptr(), _ptr(src_r), _ptr(cb), _ptr(cr), out_b.data_ptr(), _ptr(out_r),
+                                                     N, T, n_joints, count, first_output, first_frame, ratio, mode_id,
+                                                     int(max_blocks), _stream()), 'p2c_carla_resample_fwd')
+    return out_b, out_r
+
+
 # ---- K33: decoded video clips -> the pose-estimation flow's input frames (csrc/p2c_frames.hip) ---------------------------------
 FRAMES_MAX_TARGET = 1024             # the largest target size K33 is dispatched for
 

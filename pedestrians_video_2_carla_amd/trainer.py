@@ -829,15 +829,24 @@ class Trainer:
         finally:
             flow.train(was_training)
 
-    def predict_carla(self, flow, batches: Iterable, ik: bool = False) -> List:
+    def predict_carla(self, flow, batches: Iterable, ik: bool = False, src_fps=None, out_fps=None) -> List:
         """The predict loop for a CARLA player: per batch ``(bones (B,T,26,6), root (B,T,6), meta)``, the rows
         ``export_clips(flow.predict_step(batch))`` would give, left on the batch's device. A LinearAE flow takes one launch per
         batch (K32, ``walker_control.carla_lifter.CarlaLifter``); other movements models the composed path. A movements model
         that outputs absolute locations has no bone rotations to export and raises ``KeyError``; with ``ik=True`` such a flow
         goes through ``walker_control.location_retargeter.LocationRetargeter`` instead: model -> pose head -> the rotations
-        fitted to the predicted locations (K36, one launch per batch). Eval mode, no gradients, the flow's train / eval mode is
+        fitted to the predicted locations (K36, one launch per batch). ``src_fps`` and ``out_fps``, given together: every
+        clip's rows are resampled from the one rate to the other where they are (``CarlaResampler.resample``, K37: one more
+        launch per batch), so T becomes the clip's output count. Eval mode, no gradients, the flow's train / eval mode is
         put back afterwards."""
         from pedestrians_video_2_carla_amd.walker_control.carla_lifter import CarlaLifter
+        if (src_fps is None) != (out_fps is None):
+            raise ValueError('predict_carla: src_fps and out_fps come together or not at all')
+        if out_fps is None:
+            rate = lambda bones, root: (bones, root)                               # noqa: E731
+        else:
+            from pedestrians_video_2_carla_amd.walker_control.resample import CarlaResampler
+            rate = CarlaResampler(src_fps, out_fps).resample
         lifter = CarlaLifter(flow)
         was_training = flow.training
         flow.eval()
@@ -847,8 +856,8 @@ class Trainer:
                     from pedestrians_video_2_carla_amd.walker_control.location_retargeter import LocationRetargeter
                     fit = LocationRetargeter()
                     fit.check_flow(flow)
-                    return [(*fit.lift(flow, batch), batch[2]) for batch in batches]
-                return [(*lifter.lift(batch[0], batch[2]), batch[2]) for batch in batches]
+                    return [(*rate(*fit.lift(flow, batch)), batch[2]) for batch in batches]
+                return [(*rate(*lifter.lift(batch[0], batch[2])), batch[2]) for batch in batches]
         finally:
             flow.train(was_training)
             lifter.close()

@@ -26,10 +26,11 @@ def transform_from_row(row) -> 'carla.Transform':
     return carla.Transform(location=carla.Location(x=x, y=y, z=z), rotation=carla.Rotation(pitch=pitch, yaw=yaw, roll=roll))
 
 
-def export_clips(outputs) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+def export_clips(outputs, resample=None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
     """``outputs``: what ``flow.predict_step`` returns -- ``(sliced, meta)`` or ``sliced`` alone -- with ``relative_pose_loc``
     (B,T,J,3) and ``relative_pose_rot`` (B,T,J,3,3), and ``world_loc`` (B,T,3) / ``world_rot`` (B,T,3,3) when the flow has them.
-    Returns host arrays ``bones`` (B,T,J,6) and ``root`` (B,T,6) or None: one ``carla_pose_export`` call, one copy."""
+    Returns host arrays ``bones`` (B,T,J,6) and ``root`` (B,T,6) or None: one ``carla_pose_export`` call, one copy.
+    ``resample``: ``(bones, root) -> (bones, root)`` applied where the rows are, before the copy (``CarlaResampler.resample``)."""
     sliced = outputs[0] if isinstance(outputs, (tuple, list)) else outputs
     loc, rot = sliced.get('relative_pose_loc'), sliced.get('relative_pose_rot')
     if loc is None or rot is None:
@@ -39,6 +40,8 @@ def export_clips(outputs) -> Tuple[np.ndarray, Optional[np.ndarray]]:
     if wl is None or wr is None:
         wl = wr = None
     bones, root = ops.carla_pose_export(loc, rot, wl, wr)
+    if resample is not None:
+        bones, root = resample(bones, root)
     if root is None:
         return bones.cpu().numpy(), None
     rows = torch.cat((bones, root.unsqueeze(-2)), -2).cpu().numpy()          # bones and root travel together

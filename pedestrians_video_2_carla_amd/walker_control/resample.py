@@ -1,0 +1,230 @@
+"""CARLA rows at another frame rate: the definition of K37 and the streaming resampler on top of ``ops.resample_carla_rows``.
+
+The rows the exporters write -- ``bones`` (N,T,J,6) and ``root`` (N,T,6), each (x, y, z, pitch, yaw, roll) -- carry the rate of
+their source (video 30 / 29.97 fps, mocap 60 / 120 fps); a CARLA server in synchronous mode ticks at its own
+``fixed_delta_seconds`` and a player sets one pose per tick. Repeating or dropping frames stutters, and interpolating Euler
+angles is wrong across the +-180 degree seam and near +-90 degrees of pitch.
+
+Time base. ``ratio = src_fps / dst_fps`` (one fp64 division). Output sample ``k``, a global index counted from the start of the
+video, sits at source position ``p_k = fl64(k * ratio)`` (one fp64 multiplication), ``i0 = floor(p_k)``,
+``frac = float32(p_k - i0)``. A video whose last frame has global index ``g_last`` yields exactly the outputs with
+``p_k <= g_last``. Positions are always formed from global indices: that is what makes a cut video give the uncut video's
+samples.
+
+Sample, ``mode='slerp'``. ``frac == 0``: source row ``i0``, copied bit for bit (equal rates are the identity, integer decimation
+is a gather). Otherwise rows ``a = i0`` and ``b = i0 + 1``: locations ``a + frac (b - a)``; rotations as unit quaternions (w first,
+``q = qx(e0) qy(e1) qz(e2)``, ``(e0, e1, e2) = radians(-roll, -pitch, -yaw)``: the quaternion of the matrix
+``ops.carla_pose_import`` returns), ``d = qa . qb``, ``qb`` and ``d`` negated when ``d < 0`` (the shortest arc), ``d`` clamped to
+``<= 1``, weights ``(1 - frac, frac)`` when ``d > 0.99999`` and ``sin((1 - frac) t) / sin t``, ``sin(frac t) / sin t`` with
+``t = acos(d)`` otherwise, the sum normalised, and the row read back from the five matrix entries ``ops.carla_pose_export``
+reads. Comparisons, never min / max: a NaN in a neighbour reaches that output row and nothing else.
+``mode='hold'``: row ``i0``, copied -- what a player that repeats and drops frames shows.
+"""
+import math
+from typing import Optional, Tuple
+
+import torch
+from torch import Tensor
+
+from pedestrians_video_2_carla_amd import ops
+
+MODES = {'slerp': 0, 'hold': 1}
+RATIO_MIN, RATIO_MAX = 2.0 ** -10, 2.0 ** 10
+LERP_ABOVE = 0.99999
+
+
+def rate_ratio(src_fps, dst_fps) -> float:
+    """``src_fps / dst_fps`` as the one fp64 value host and kernel use; refuses rates that are not positive and finite and
+    ratios outside [2^-10, 2^10]."""
+    src_fps, dst_fps = float(src_fps), float(dst_fps)
+    if not (math.isfinite(src_fps) and math.isfinite(dst_fps) and src_fps > 0.0 and dst_fps > 0.0):
+        raise ValueError(f'resample: frame rates must be positive and finite, got {src_fps} -> {dst_fps}')
+    ratio = src_fps / dst_fps
+    if not (math.isfinite(ratio) and RATIO_MIN <= ratio <= RATIO_MAX):
+        raise ValueError(f'resample: src_fps / dst_fps = {ratio} lies outside [2^-10, 2^10]')
+    return ratio
+
+
+def check_mode(mode: str) -> int:
+    if mode not in MODES:
+        raise ValueError(f'resample: mode {mode!r}; one of {tuple(MODES)} expected')
+    return MODES[mode]
+
+
+def output_count(g_last: int, ratio: float) -> int:
+    """How many outputs ``k >= 0`` have ``fl64(k * ratio) <= g_last``: a floating-point estimate corrected with the product test
+    the kernel's positions come from."""
+    g_last = int(g_last)
+    if g_last < 0:
+        return 0
+    k = int(math.floor(g_last / ratio))
+    while float(k + 1) * ratio <= g_last:
+        k += 1
+    while k >= 0 and float(k) * ratio > g_last:
+        k -= 1
+    return k + 1
+
+
+def sample_positions(first_output: int, count: int, ratio: float, device=None) -> Tuple[Tensor, Tensor]:
+    """``(i0 int64 (count), frac float32 (count))`` of the outputs ``first_output .. first_output + count - 1``."""
+    p = torch.arange(int(first_output), int(first_output) + int(count), dtype=torch.float64, device=device) * float(ratio)
+    i0 = torch.floor(p)
+    return i0.to(torch.int64), (p - i0).to(torch.float32)
+
+
+def source_span(first_output: int, count: int, ratio: float) -> Tuple[int, int]:
+    """The smallest and the largest global source index the outputs read (``i0 + 1`` only where ``frac > 0``; ``i0`` does not
+    decrease with ``k``, so the first and the last output decide)."""
+    def one(k):                  # p - i0 > 0 is at least 2^-62 here (ratio >= 2^-10, p < 2^51): its float32 value is > 0 as well
+        p = float(k) * ratio
+        i0 = math.floor(p)
+        return int(i0), p - i0 > 0.0
+    lo, _ = one(first_output)
+    hi, more = one(first_output + count - 1)
+    return lo, hi + (1 if more else 0)
+
+
+def check_rows(bones: Tensor, root: Optional[Tensor], carry, what: str = 'resample_carla_rows'):
+    """Shapes of (N,T,J,6) bones, (N,T,6) root and the carried frame ((N,J,6), (N,6) or None); returns ``(carry_bones, carry_root)``."""
+    if bones.ndim != 4 or bones.shape[-1] != 6 or bones.shape[-2] < 1:
+        raise ValueError(f'{what}: bones (N,T,J,6) with J >= 1 expected, got {tuple(bones.shape)}')
+    if root is not None and (tuple(root.shape) != tuple(bones.shape[:2]) + (6,) or root.dtype != bones.dtype
+                             or root.device != bones.device):
+        raise ValueError(f'{what}: root {tuple(root.shape)} {root.dtype} for bones {tuple(bones.shape)} {bones.dtype}; '
+                         f'{tuple(bones.shape[:2]) + (6,)} of the same dtype and device expected')
+    if carry is None:
+        return None, None
+    cb, cr = carry if isinstance(carry, (tuple, list)) else (carry, None)
+    N, _, J, _ = bones.shape
+    if cb is None or tuple(cb.shape) != (N, J, 6) or cb.dtype != bones.dtype or cb.device != bones.device:
+        raise ValueError(f'{what}: carried bones {None if cb is None else tuple(cb.shape)}; ({N},{J},6) like the bones expected')
+    if root is not None and (cr is None or tuple(cr.shape) != (N, 6) or cr.dtype != bones.dtype or cr.device != bones.device):
+        raise ValueError(f'{what}: carried root {None if cr is None else tuple(cr.shape)}; ({N},6) like the root expected')
+    return cb, (cr if root is not None else None)
+
+
+def check_span(first_output: int, count: int, ratio: float, first_frame: int, T: int, has_carry: bool, what: str):
+    if first_output < 0 or first_frame < 0 or count < 0:
+        raise ValueError(f'{what}: first_output, first_frame and count are not negative')
+    if count == 0:
+        return
+    lo, hi = source_span(first_output, count, ratio)
+    have_lo, have_hi = first_frame - (1 if has_carry else 0), first_frame + T - 1
+    if lo < have_lo or hi > have_hi:
+        raise ValueError(f'{what}: outputs {first_output}..{first_output + count - 1} read source frames {lo}..{hi}, '
+                         f'frames {have_lo}..{have_hi} are given')
+
+
+# ---- the definition on tensor ops ----------------------------------------------------------------------------------------------
+def _row_quat(rows: Tensor) -> Tensor:
+    """(...,6) rows -> (...,4) unit quaternions, w first, of Rx(e0) Ry(e1) Rz(e2), (e0, e1, e2) = radians(-roll, -pitch, -yaw)."""
+    half = torch.deg2rad(torch.stack((-rows[..., 5], -rows[..., 3], -rows[..., 4]), -1)) * 0.5
+    s, c = torch.sin(half), torch.cos(half)
+    s0, s1, s2 = s.unbind(-1)
+    c0, c1, c2 = c.unbind(-1)
+    w1, x1, y1, z1 = c0 * c1, s0 * c1, c0 * s1, s0 * s1
+    return torch.stack((w1 * c2 - z1 * s2, x1 * c2 + y1 * s2, y1 * c2 - x1 * s2, w1 * s2 + z1 * c2), -1)
+
+
+def _atan2(y: Tensor, x: Tensor) -> Tensor:
+    """``atan2(y, x)`` through the half-angle form, on unary functions only: the host's binary ``torch.atan2`` rounds differently
+    in the vector body and the scalar tail of a tensor, and a row's bits must not depend on the batch around it."""
+    r = torch.sqrt(x * x + y * y)
+    angle = 2 * torch.atan(torch.where(x >= 0, y / (r + x), (r - x) / y))          # neither sum cancels
+    return torch.where(r == 0, torch.zeros_like(r), angle)
+
+
+def interpolate_rows(a: Tensor, b: Tensor, frac: Tensor) -> Tensor:
+    """Rows ``a`` and ``b`` (...,6) combined at ``frac`` (broadcast against the leading dimensions, the rows' dtype): the
+    ``frac > 0`` arm of the definition."""
+    f = frac.unsqueeze(-1)
+    loc = a[..., :3] + f * (b[..., :3] - a[..., :3])
+    qa, qb = _row_quat(a), _row_quat(b)
+    d = (qa * qb).sum(-1, keepdim=True)
+    flip = d < 0
+    qb, d = torch.where(flip, -qb, qb), torch.where(flip, -d, d)
+    d = torch.where(d > 1, torch.ones_like(d), d)
+    theta = torch.acos(d)
+    inv = 1.0 / torch.sin(theta)
+    lerp = d > LERP_ABOVE
+    wa = torch.where(lerp, 1.0 - f, torch.sin((1.0 - f) * theta) * inv)
+    wb = torch.where(lerp, f + torch.zeros_like(d), torch.sin(f * theta) * inv)
+    q = wa * qa + wb * qb
+    q = q / torch.sqrt((q * q).sum(-1, keepdim=True))
+    w, x, y, z = q.unbind(-1)
+    r00, r01, r02 = 1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)
+    r12, r22 = 2 * (y * z - w * x), 1 - 2 * (x * x + y * y)
+    one = torch.ones_like(r02)
+    r02 = torch.where(r02 > 1, one, torch.where(r02 < -1, -one, r02))
+    e1, e0, e2 = torch.asin(r02), _atan2(-r12, r22), _atan2(-r01, r00)
+    return torch.cat((loc, torch.stack((-torch.rad2deg(e1), -torch.rad2deg(e2), -torch.rad2deg(e0)), -1)), -1)
+
+
+def _resample_one(src: Tensor, ia: Tensor, ib: Tensor, frac: Tensor, hold: bool) -> Tensor:
+    """``src`` (N,S,...,6), positions (K) into its second dimension -> (N,K,...,6)."""
+    a = src.index_select(1, ia)
+    if hold:
+        return a
+    f = frac.to(src.dtype).reshape((-1,) + (1,) * (src.ndim - 3))
+    exact = (frac == 0).reshape(f.shape).unsqueeze(-1)
+    return torch.where(exact, a, interpolate_rows(a, src.index_select(1, ib), f))
+
+
+@torch.no_grad()
+def resample_rows(bones: Tensor, root: Optional[Tensor], carry_bones: Optional[Tensor], carry_root: Optional[Tensor], ratio: float,
+                  hold: bool, first_frame: int, first_output: int, count: int) -> Tuple[Tensor, Optional[Tensor]]:
+    """The definition, on the tensors' device and in their dtype, behind the checks of ``ops.resample_carla_rows``: ``count``
+    outputs from ``first_output`` on, of frames ``first_frame ..`` with ``carry_*`` (or None) as frame ``first_frame - 1``."""
+    i0, frac = sample_positions(first_output, count, ratio, bones.device)
+    has_carry = carry_bones is not None
+    ia = i0 - (first_frame - (1 if has_carry else 0))
+    ib = ia + (frac > 0).to(torch.int64)                      # row i0 + 1 is read only where it is needed: the caller checked the span
+    src_b = torch.cat((carry_bones.unsqueeze(1), bones), 1) if has_carry else bones
+    out_b = _resample_one(src_b, ia, ib, frac, hold)
+    if root is None:
+        return out_b, None
+    src_r = torch.cat((carry_root.unsqueeze(1), root), 1) if has_carry else root
+    return out_b, _resample_one(src_r, ia, ib, frac, hold)
+
+
+# ---- the streaming resampler ---------------------------------------------------------------------------------------------------
+class CarlaResampler:
+    """``CarlaResampler(src_fps, dst_fps, mode).resample(bones, root)``: every clip its own video, stateless.
+    ``push(bones, root)`` / ``reset()`` stream the same N videos chunk by chunk (any chunk length >= 1): the outputs that became
+    computable come back, possibly none, and the concatenated outputs are those of the uncut video. The state is the last source
+    frame of each video, left on its device, and two integers: frames seen and outputs emitted. One carried frame always suffices:
+    the previous push emitted every k with p_k <= g0 - 1, so the rest have i0 >= g0 - 1."""
+
+    def __init__(self, src_fps, dst_fps, mode: str = 'slerp'):
+        self.src_fps, self.dst_fps, self.mode = float(src_fps), float(dst_fps), mode
+        self.ratio = rate_ratio(src_fps, dst_fps)
+        check_mode(mode)
+        self.reset()
+
+    def reset(self):
+        """The next ``push`` starts new videos."""
+        self._carry = None
+        self._layout = None
+        self.frames = 0          # source frames seen: the global index of the next chunk's first frame
+        self.outputs = 0         # outputs emitted: the global index of the next output
+
+    def resample(self, bones: Tensor, root: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
+        return ops.resample_carla_rows(bones, root, src_fps=self.src_fps, dst_fps=self.dst_fps, mode=self.mode)
+
+    def push(self, bones: Tensor, root: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
+        check_rows(bones, root, None, 'CarlaResampler.push')
+        N, T, J, _ = bones.shape
+        if T < 1:
+            raise ValueError('CarlaResampler.push: a chunk holds at least one frame')
+        layout = (N, J, root is not None)
+        if self._layout is not None and layout != self._layout:
+            raise RuntimeError(f'CarlaResampler.push: (videos, bones, root) = {layout} after {self._layout}; '
+                               'reset() starts other videos')
+        total = output_count(self.frames + T - 1, self.ratio)
+        out = ops.resample_carla_rows(bones, root, src_fps=self.src_fps, dst_fps=self.dst_fps, mode=self.mode, carry=self._carry,
+                                      first_frame=self.frames, first_output=self.outputs, count=total - self.outputs)
+        self._carry = (bones[:, -1].detach().clone(), root[:, -1].detach().clone() if root is not None else None)
+        self._layout = layout
+        self.frames += T
+        self.outputs = total
+        return out
