@@ -235,6 +235,26 @@ P2C_API int64_t p2c_mlp_workspace_floats(const p2c_mlp_desc *desc);
 P2C_API int64_t p2c_mlp_saved_floats(const p2c_mlp_desc *desc);
 P2C_API int p2c_mlp_fwd(const p2c_mlp_desc *desc, void *stream);
 P2C_API int p2c_mlp_bwd(const p2c_mlp_desc *desc, void *stream);
+/* What p2c_mlp_fwd / p2c_mlp_bwd would do for desc->dims, n_layers and N with fp32 operands, from the functions they decide with
+ * (the environment overrides included). Geometry only: no pointer of desc is looked at and nothing is launched. Writes
+ * P2C_MLP_PLAN_INTS values to the HOST array out; returns 0, or P2C_E_SHAPE for a layer count, width or N outside the ABI. */
+enum {
+  P2C_MLP_PLAN_PROVIDER = 0,         /* kernels' shape provider: 0 = generic, 1 / 2 / 3 = the LinearAE shapes ending in 156 / 78 / 52 */
+  P2C_MLP_PLAN_WAVE_FORWARD = 1,     /* 1 = wave-per-tile forward, 0 = cooperative */
+  P2C_MLP_PLAN_SPLIT_WGRAD = 2,      /* 1 = factors + contraction + small reduction, 0 = weight gradient fused into the backward */
+  P2C_MLP_PLAN_SAVE_ACTIVATIONS = 3, /* 1 = the forward leaves the hidden activations (given desc->saved), 0 = recomputed */
+  P2C_MLP_PLAN_FWD_BLOCKS = 4,       /* workgroups of the forward and of the backward kernel */
+  P2C_MLP_PLAN_BWD_BLOCKS = 5,
+  P2C_MLP_PLAN_TILES_W = 6,          /* 16x16 tiles of the augmented weight gradients */
+  P2C_MLP_PLAN_W_TOTAL = 7,          /* floats of the packed image (p2c_mlp_image_floats) */
+  P2C_MLP_PLAN_LDS_FWD = 8,          /* bytes of LDS: cooperative forward, backward, wave-per-tile forward */
+  P2C_MLP_PLAN_LDS_BWD = 9,
+  P2C_MLP_PLAN_LDS_FWD_WAVE = 10,
+  P2C_MLP_PLAN_FWD_OK = 11,          /* 1 = the geometry is one p2c_mlp_fwd / p2c_mlp_bwd accepts, 0 = it returns P2C_E_SHAPE */
+  P2C_MLP_PLAN_BWD_OK = 12,
+  P2C_MLP_PLAN_INTS = 16
+};
+P2C_API int p2c_mlp_plan(const p2c_mlp_desc *desc, int32_t *out);
 
 /* ---- K13: the small-batch train step of LitPoseLiftingFlow(LinearAE) in two launches ------------------------------------
  * Replaces, for one optimisation step on a batch of B clips of T <= 16 frames (one clip = one 16-sample MFMA tile):

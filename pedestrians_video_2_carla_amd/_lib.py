@@ -41,6 +41,10 @@ class PoseHeadDesc(ctypes.Structure):
 
 
 P2C_MLP_MAX_LAYERS = 8
+# what p2c_mlp_plan writes (the P2C_MLP_PLAN_* indices of include/p2c.h, in order) into P2C_MLP_PLAN_INTS values
+P2C_MLP_PLAN_FIELDS = ('provider', 'wave_forward', 'split_wgrad', 'save_activations', 'fwd_blocks', 'bwd_blocks', 'tiles',
+                       'image_floats', 'lds_fwd', 'lds_bwd', 'lds_fwd_wave', 'fwd_ok', 'bwd_ok')
+P2C_MLP_PLAN_INTS = 16
 
 
 class MlpDesc(ctypes.Structure):
@@ -337,6 +341,7 @@ SYMBOLS = {
     'p2c_atb_group': (ctypes.c_int, [ctypes.POINTER(AtbProblem), _i32, _vp, _vp]),
     'p2c_mlp_fwd': (ctypes.c_int, [ctypes.POINTER(MlpDesc), _vp]),
     'p2c_mlp_bwd': (ctypes.c_int, [ctypes.POINTER(MlpDesc), _vp]),
+    'p2c_mlp_plan': (ctypes.c_int, [ctypes.POINTER(MlpDesc), _ip]),
     'p2c_train_step_supported': (ctypes.c_int, [ctypes.POINTER(TrainStepDesc)]),
     'p2c_train_step_workspace_floats': (_i64, [ctypes.POINTER(TrainStepDesc)]),
     'p2c_train_step': (ctypes.c_int, [ctypes.POINTER(TrainStepDesc), ctypes.POINTER(_vp * 3), _vp]),

@@ -589,13 +589,12 @@ using namespace p2c_mlp;
 
 using p2c_host::aligned16;
 
-static int fill(MlpArgs &a, const p2c_mlp_desc *d) {
-  if (!d || !d->x) return P2C_E_NULL;
+// geometry only (no pointer is looked at): 0, or P2C_E_SHAPE for a layer count, a width or a row count outside the ABI
+static int fill_shape(MlpArgs &a, const p2c_mlp_desc *d) {
   if (d->n_layers < 1 || d->n_layers > P2C_MLP_MAX_LAYERS || d->N < 0) return P2C_E_SHAPE;
   a = MlpArgs{};
   a.n_layers = d->n_layers;
   a.N = d->N;
-  a.x = d->x, a.y = d->y, a.gy = d->gy, a.partials = d->partials, a.w_image = d->w_image, a.saved = d->saved;
   int rows = 0, tiles = 0, params = 0, wtot = 0;
   for (int l = 0; l <= d->n_layers; ++l) {
     if (d->dims[l] < 1 || d->dims[l] > MAXW - 1) return P2C_E_SHAPE;
@@ -604,8 +603,6 @@ static int fill(MlpArgs &a, const p2c_mlp_desc *d) {
     rows += act_rows_of(a.dims[l]);            // room for the ones row / the 4-step k rounding past pad16
   }
   for (int l = 0; l < d->n_layers; ++l) {
-    if (!d->W[l] || !d->b[l]) return P2C_E_NULL;
-    a.W[l] = d->W[l], a.b[l] = d->b[l], a.gW[l] = d->gW[l], a.gb[l] = d->gb[l];
     tiles += ((a.dims[l + 1] + 15) / 16) * ((a.dims[l] + 1 + 15) / 16);
     params += a.dims[l + 1] * (a.dims[l] + 1);
     a.ld[l] = ld_of(a.dims[l]);
@@ -639,6 +636,18 @@ static int fill(MlpArgs &a, const p2c_mlp_desc *d) {
         }
     }
     for (; t < MAX_SLOTS * WAVES; ++t) a.tab[2 * t] = a.tab[0], a.tab[2 * t + 1] = a.tab[1];
+  }
+  return 0;
+}
+// the geometry, then the pointers. An empty batch (N == 0) has no rows to point at: x may be null there.
+static int fill(MlpArgs &a, const p2c_mlp_desc *d) {
+  if (!d || (!d->x && d->N != 0)) return P2C_E_NULL;
+  const int rc = fill_shape(a, d);
+  if (rc) return rc;
+  a.x = d->x, a.y = d->y, a.gy = d->gy, a.partials = d->partials, a.w_image = d->w_image, a.saved = d->saved;
+  for (int l = 0; l < d->n_layers; ++l) {
+    if (!d->W[l] || !d->b[l]) return P2C_E_NULL;
+    a.W[l] = d->W[l], a.b[l] = d->b[l], a.gW[l] = d->gW[l], a.gb[l] = d->gb[l];
   }
   const int n0 = a.dims[0], nL = a.dims[d->n_layers];
   a.vec_x = (n0 % 4 == 0) && aligned16(a.x);
@@ -707,13 +716,22 @@ static mlp_kernel_t pick_wave_of() {
 }
 // reduced-precision arms: LinearAE with the 6-D rotation output only (BASELINE.json configs[1]); nullptr = not available
 static bool reduced_ok(const MlpArgs &a) { return !force_generic() && LinearAE156::matches(a); }
+// the shape provider of the fp32 kernels (P2C_MLP_PLAN_PROVIDER): 0 = DynShape, 1 / 2 / 3 = LinearAE156 / 78 / 52
+static int provider(const MlpArgs &a) {
+  if (!force_generic()) {
+    if (LinearAE156::matches(a)) return 1;
+    if (LinearAE78::matches(a)) return 2;
+    if (LinearAE52::matches(a)) return 3;
+  }
+  return 0;
+}
 static mlp_kernel_t pick_wave(const MlpArgs &a, int prec) {
   if (prec == P2C_PREC_BF16) return reduced_ok(a) ? pick_wave_of<LinearAE156, P2C_PREC_BF16>() : nullptr;
   if (prec == P2C_PREC_BF16X3) return reduced_ok(a) ? pick_wave_of<LinearAE156, P2C_PREC_BF16X3>() : nullptr;
-  if (!force_generic()) {
-    if (LinearAE156::matches(a)) return pick_wave_of<LinearAE156>();
-    if (LinearAE78::matches(a)) return pick_wave_of<LinearAE78>();
-    if (LinearAE52::matches(a)) return pick_wave_of<LinearAE52>();
+  switch (provider(a)) {
+    case 1: return pick_wave_of<LinearAE156>();
+    case 2: return pick_wave_of<LinearAE78>();
+    case 3: return pick_wave_of<LinearAE52>();
   }
   return pick_wave_of<DynShape>();
 }
@@ -736,10 +754,10 @@ static mlp_kernel_t pick_of(bool bwd, bool factors, bool saved) {
 static mlp_kernel_t pick(const MlpArgs &a, int prec, bool bwd, bool factors = false, bool saved = false) {
   if (prec == P2C_PREC_BF16) return reduced_ok(a) ? pick_of<LinearAE156, P2C_PREC_BF16>(bwd, factors, saved) : nullptr;
   if (prec == P2C_PREC_BF16X3) return reduced_ok(a) ? pick_of<LinearAE156, P2C_PREC_BF16X3>(bwd, factors, saved) : nullptr;
-  if (!force_generic()) {
-    if (LinearAE156::matches(a)) return pick_of<LinearAE156>(bwd, factors, saved);
-    if (LinearAE78::matches(a)) return pick_of<LinearAE78>(bwd, factors, saved);
-    if (LinearAE52::matches(a)) return pick_of<LinearAE52>(bwd, factors, saved);
+  switch (provider(a)) {
+    case 1: return pick_of<LinearAE156>(bwd, factors, saved);
+    case 2: return pick_of<LinearAE78>(bwd, factors, saved);
+    case 3: return pick_of<LinearAE52>(bwd, factors, saved);
   }
   return pick_of<DynShape>(bwd, factors, saved);
 }
@@ -848,27 +866,60 @@ extern "C" int64_t p2c_mlp_workspace_floats(const p2c_mlp_desc *d) {
   return split_wgrad(a.N) && split_floats(a) > fused ? split_floats(a) : fused;
 }
 
+// What the geometry alone decides about a launch; p2c_mlp_fwd / p2c_mlp_bwd and p2c_mlp_plan ask the same functions.
+constexpr size_t LDS_LIMIT = 160 * 1024;
+static int fwd_shape_rc(const MlpArgs &a) { return lds_fwd(a) > LDS_LIMIT ? P2C_E_SHAPE : 0; }
+static int bwd_shape_rc(const MlpArgs &a) {
+  return (a.n_tiles_w > MAX_SLOTS * WAVES || lds_bwd(a) > LDS_LIMIT) ? P2C_E_SHAPE : 0;
+}
+static int fwd_blocks(const MlpArgs &a) {             // workgroups of the forward: four sample tiles each in the wave form
+  if (!wave_forward(a)) return n_blocks(a.N);
+  const int64_t groups = ((a.N + TS - 1) / TS + FW_WAVES - 1) / FW_WAVES;
+  const int cap = max_blocks();
+  return (int)(groups < cap ? groups : cap);
+}
+
+extern "C" int p2c_mlp_plan(const p2c_mlp_desc *d, int32_t *out) {
+  if (!d || !out) return P2C_E_NULL;
+  MlpArgs a;
+  const int rc = fill_shape(a, d);
+  if (rc) return rc;
+  for (int i = 0; i < P2C_MLP_PLAN_INTS; ++i) out[i] = 0;
+  out[P2C_MLP_PLAN_PROVIDER] = provider(a);
+  out[P2C_MLP_PLAN_WAVE_FORWARD] = wave_forward(a);
+  out[P2C_MLP_PLAN_SPLIT_WGRAD] = split_wgrad(a.N);
+  out[P2C_MLP_PLAN_SAVE_ACTIVATIONS] = save_activations(a);
+  out[P2C_MLP_PLAN_FWD_BLOCKS] = fwd_blocks(a);
+  out[P2C_MLP_PLAN_BWD_BLOCKS] = n_blocks(a.N);
+  out[P2C_MLP_PLAN_TILES_W] = a.n_tiles_w;
+  out[P2C_MLP_PLAN_W_TOTAL] = a.w_total;
+  out[P2C_MLP_PLAN_LDS_FWD] = (int32_t)lds_fwd(a);
+  out[P2C_MLP_PLAN_LDS_BWD] = (int32_t)lds_bwd(a);
+  out[P2C_MLP_PLAN_LDS_FWD_WAVE] = (int32_t)lds_fwd_wave(a);
+  out[P2C_MLP_PLAN_FWD_OK] = fwd_shape_rc(a) == 0;
+  out[P2C_MLP_PLAN_BWD_OK] = bwd_shape_rc(a) == 0;
+  return 0;
+}
+
 extern "C" int p2c_mlp_fwd(const p2c_mlp_desc *d, void *stream_) {
   MlpArgs a;
   int rc = fill(a, d);
   if (rc) return rc;
-  if (!a.y || !a.w_image) return P2C_E_NULL;
+  if ((!a.y && a.N != 0) || !a.w_image) return P2C_E_NULL;
   if (a.N == 0) return 0;
   if (a.saved && !save_activations(a)) a.saved = nullptr;      // same rule on both sides of the autograd edge
   const size_t lds = lds_fwd(a);
-  if (lds > 160 * 1024) return P2C_E_SHAPE;
+  if (fwd_shape_rc(a)) return P2C_E_SHAPE;
   allow_big_lds();
   if (!d->skip_pack)
     hipLaunchKernelGGL(mlp_pack_kernel, dim3((a.w_total + 255) / 256), dim3(256), 0, (hipStream_t)stream_, a);
   const int prec = d->precision;
   if (prec < P2C_PREC_F32 || prec > P2C_PREC_BF16X3 || (prec != P2C_PREC_F32 && !reduced_ok(a))) return P2C_E_ENUM;
   if (wave_forward(a)) {
-    const int64_t groups = ((a.N + TS - 1) / TS + FW_WAVES - 1) / FW_WAVES;
-    const int cap = max_blocks();
-    hipLaunchKernelGGL(pick_wave(a, prec), dim3((unsigned)(groups < cap ? groups : cap)), dim3(64 * FW_WAVES), lds_fwd_wave(a),
+    hipLaunchKernelGGL(pick_wave(a, prec), dim3((unsigned)fwd_blocks(a)), dim3(64 * FW_WAVES), lds_fwd_wave(a),
                        (hipStream_t)stream_, a);
   } else {
-    hipLaunchKernelGGL(pick(a, prec, false), dim3(n_blocks(a.N)), dim3(64 * WAVES), lds, (hipStream_t)stream_, a);
+    hipLaunchKernelGGL(pick(a, prec, false), dim3(fwd_blocks(a)), dim3(64 * WAVES), lds, (hipStream_t)stream_, a);
   }
   return p2c_host::launch_status();
 }
@@ -877,14 +928,13 @@ extern "C" int p2c_mlp_bwd(const p2c_mlp_desc *d, void *stream_) {
   MlpArgs a;
   int rc = fill(a, d);
   if (rc) return rc;
-  if (!a.gy || !a.partials || !a.w_image) return P2C_E_NULL;
+  if ((!a.gy && a.N != 0) || !a.partials || !a.w_image) return P2C_E_NULL;
   for (int l = 0; l < a.n_layers; ++l)
     if (!a.gW[l] || !a.gb[l]) return P2C_E_NULL;
-  if (a.n_tiles_w > MAX_SLOTS * WAVES) return P2C_E_SHAPE;
+  if (bwd_shape_rc(a)) return P2C_E_SHAPE;
   const int prec = d->precision;
   if (prec < P2C_PREC_F32 || prec > P2C_PREC_BF16X3 || (prec != P2C_PREC_F32 && !reduced_ok(a))) return P2C_E_ENUM;
   const size_t lds = lds_bwd(a);
-  if (lds > 160 * 1024) return P2C_E_SHAPE;
   int blocks = n_blocks(a.N);
   p2c_optim::Coefs *coefs = nullptr;
   allow_big_lds();

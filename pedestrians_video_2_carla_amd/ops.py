@@ -685,10 +685,72 @@ def _mlp_desc(x, weights, biases):
     return d
 
 
-def mlp_supported(dims: Sequence[int]) -> bool:
-    """Widths the kernel handles: every layer < 160 wide and at most 96 16x16 weight-gradient tiles."""
+MLP_LDS_LIMIT = 160 * 1024      # bytes of LDS a workgroup of the fused MLP may ask for (csrc/p2c_mlp.hip)
+_MLP_TP, _MLP_FW_WAVES = 17, 4    # TP (p2c_mlp_dev.h), FW_WAVES (p2c_mlp.hip)
+
+
+def mlp_geometry(dims: Sequence[int]) -> dict:
+    """The layout arithmetic of csrc/p2c_mlp.hip (fill(), lds_fwd(), lds_bwd(), lds_fwd_wave()) for the widths ``dims``, in pure
+    Python (the callers of ``mlp_supported`` may run before the library is loaded): ``tiles`` (16x16 tiles of the augmented weight
+    gradients), ``image_floats`` (the packed weight image) and the bytes of LDS of the cooperative forward, the backward and the
+    wave-per-tile forward. tests/test_mlp_cells_gpu.py holds it to ``p2c_mlp_plan``."""
+    dims = [int(v) for v in dims]
+    nl = len(dims) - 1
+
+    def pad16(n):
+        return (n + 15) & ~15
+
+    def ld_of(n_in):                    # pitch of a layer's image: k extent with the bias column, == 2 (mod 4)
+        ld = max(((((n_in + 1 + 3) >> 2) + 3) & ~3) * 4, pad16(n_in))
+        while ld & 3 != 2:
+            ld += 1
+        return ld
+
+    def img_rows_of(n_out):
+        return (n_out + 16) & ~15
+
+    def act_rows_of(n):
+        return pad16(n) + 16
+
     tiles = sum(((o + 15) // 16) * ((i + 1 + 15) // 16) for i, o in zip(dims[:-1], dims[1:]))
-    return len(dims) - 1 <= 8 and max(dims) < 160 and tiles <= 96
+    image = (sum(img_rows_of(o) * ld_of(i) for i, o in zip(dims[:-1], dims[1:])) + 3) & ~3
+    h_off = [0]
+    for n in dims:
+        h_off.append(h_off[-1] + act_rows_of(n))          # h_off[nl + 1] = rows of H_0 .. H_L
+    rows_a = max([act_rows_of(n) for n in dims[0:nl:2]], default=0)      # wave forward: H_l lives in buffer l & 1
+    rows_b = max([act_rows_of(n) for n in dims[1:nl:2]], default=0)
+    return dict(tiles=tiles, image_floats=image,
+                lds_fwd=4 * (image + h_off[nl] * _MLP_TP),
+                lds_bwd=4 * (image + (h_off[nl] + h_off[nl + 1] - h_off[1]) * _MLP_TP),
+                lds_fwd_wave=4 * (image + _MLP_FW_WAVES * (rows_a + rows_b) * _MLP_TP))
+
+
+def mlp_supported(dims: Sequence[int]) -> bool:
+    """Stacks whose forward AND backward the kernel accepts: 1 to 8 layers, every width in 1 .. 159, at most 96 16x16
+    weight-gradient tiles, and the LDS of either direction within 160 KB."""
+    dims = list(dims)
+    if not 1 <= len(dims) - 1 <= 8 or min(dims) < 1 or max(dims) >= 160:
+        return False
+    g = mlp_geometry(dims)
+    return g['tiles'] <= 96 and g['lds_fwd'] <= MLP_LDS_LIMIT and g['lds_bwd'] <= MLP_LDS_LIMIT
+
+
+def mlp_plan(dims: Sequence[int], rows: int) -> Optional[dict]:
+    """What the library would run for a stack of widths ``dims`` on ``rows`` rows in this process (``p2c_mlp_plan``: the kernels'
+    shape provider, forward form, weight-gradient form, saved activations, grids, LDS, whether either direction is accepted), as
+    a dict keyed by ``_lib.P2C_MLP_PLAN_FIELDS``; None for a layer count or a width outside the ABI. Launches nothing."""
+    d = _lib.MlpDesc()
+    if not 1 <= len(dims) - 1 <= _lib.P2C_MLP_MAX_LAYERS:
+        return None
+    d.n_layers, d.N = len(dims) - 1, int(rows)
+    for i, v in enumerate(dims):
+        d.dims[i] = int(v)
+    out = (ctypes.c_int32 * _lib.P2C_MLP_PLAN_INTS)()
+    rc = _lib.lib().p2c_mlp_plan(ctypes.byref(d), out)
+    if rc == -2:
+        return None
+    _lib.check(rc, 'p2c_mlp_plan')
+    return dict(zip(_lib.P2C_MLP_PLAN_FIELDS, out))
 
 
 class FusedMLPFunction(torch.autograd.Function):

@@ -32,9 +32,10 @@ def _ints(gen, shape, p_nonzero):
     return (sign * keep).double()
 
 
-def _case(dims, rows):
-    """Inputs and the fp64 results of one case, with the largest sum of absolute products met anywhere."""
-    gen = torch.Generator().manual_seed(1000 * len(dims) + 10 * dims[-1] + rows)
+def _case(dims, rows, salt=0):
+    """Inputs and the fp64 results of one case, with the largest sum of absolute products met anywhere. `salt` picks another draw
+    of the same distribution (tests/test_mlp_cells_gpu.py: a draw whose results are not all zero)."""
+    gen = torch.Generator().manual_seed(1000 * len(dims) + 10 * dims[-1] + rows + 1000003 * salt)
     Ws = [_ints(gen, (o, i), 0.5) for i, o in zip(dims[:-1], dims[1:])]
     bs = [_ints(gen, (o,), 0.5) for o in dims[1:]]
     x, gy = _ints(gen, (rows, dims[0]), 0.75), _ints(gen, (rows, dims[-1]), 0.75)
