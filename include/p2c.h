@@ -1203,6 +1203,50 @@ P2C_API int p2c_carla_resample_fwd(const float *bones, const float *root, const 
                                    int64_t first_output, int64_t first_frame, double ratio, int32_t mode, int32_t max_blocks,
                                    void *stream);
 
+/* ---- K38: Carla2D3D training batches generated on the device in one launch (csrc/p2c_generate.hip) --------------------------
+ * The reference's infinite training set (data/carla/datasets/carla_2d3d_dataset.py:145-210, Carla2D3DIterableDataset.generate_batch)
+ * for clips first_clip .. first_clip + B - 1 of (seed, draw_stream). Every random number is a pure function of (seed, draw_stream,
+ * clip index, frame, joint, channel): the key schedule and what is made of a word are defined in
+ * pedestrians_video_2_carla_amd/data/carla/generator.py, which this entry point equals to the bit. Nothing is read from the device
+ * but the reference tables; there is no state.
+ *   random_changes_each_frame in [0, 26] joints per frame get Euler angles (2u - 1) max_change_rad; the world's yaw changes by
+ *   (2u - 1) max_initial_world_rot_change_rad in frame 0 when that is > 0 and by (2u - 1) max_world_rot_change_rad in later frames
+ *   when that is != 0; with both 0 the world is the identity and takes no part in the projection.
+ *   transform  P2C_TRANSFORM_*, the data-side normaliser (p2c_collate_fwd's, CARLA hips / neck joints); noise P2C_GENERATE_NOISE_*:
+ *   UNIFORM adds u noise_param - noise_param / 2 per channel; miss_prob: NULL or 26 HOST floats, joint j of a frame becomes (0, 0)
+ *   where its draw u < miss_prob[j]. camera: 5 HOST floats (f, cx, cy, distance, elevation). ref_rel_loc (4,26,3), ref_rel_rot
+ *   (4,26,3,3): the reference tables on the device.
+ * Per clip: skeleton type = the top two bits of the clip's word; rel[t] = C[t] rel[t-1] from the type's ref_rel_rot; absolute pose
+ * by forward kinematics (row vectors); world_rot[t] = world_rot[t-1] Rz(yaw[t]); projection as p2c_pose_head_fwd; then the tail of
+ * p2c_collate_fwd: projection_2d_deformed = projection_2d + noise with missing joints zeroed, frames = normalise(deformed),
+ * projection_2d_transformed / _shift / _scale = normalise(projection_2d).
+ * Outputs, each NULL or given, only the given ones are written, and what is written does not depend on which others are asked for:
+ * frames, projection_2d, projection_2d_deformed, projection_2d_transformed (B,T,26,2); projection_2d_shift (B,T,2);
+ * projection_2d_scale (B,T); pose_changes, relative_pose_rot, absolute_pose_rot (B,T,26,3,3); relative_pose_loc, absolute_pose_loc
+ * (B,T,26,3); world_loc, world_loc_changes (B,T,3: zeros); world_rot, world_rot_changes (B,T,3,3); skel_type (B) int32.
+ * mapping  P2C_GENERATE_SEQUENTIAL: a 32-lane group per clip walks its frames; P2C_GENERATE_FRAME_PARALLEL: a group per (clip,
+ *   frame) replays the draws and running products of the frames before its own; P2C_GENERATE_AUTO: the latter up to
+ *   P2C_GENERATE_FRAME_PARALLEL_MAX_FRAMES frames in the batch. Both give the same bits.
+ * max_blocks  0: the kernel's own grid cap; > 0 lowers it (groups stride over clips, or over frames).
+ * One writer per element, no atomics, no LDS: two runs give the same bits. In this order, before anything is launched: P2C_E_SHAPE
+ * for B < 0, T outside [1, P2C_GENERATE_MAX_T], first_clip < 0, B T > 2^40, random_changes_each_frame outside [0, 26],
+ * max_blocks < 0; P2C_E_ENUM for another transform, noise or mapping, or a transformed / shift / scale output with
+ * P2C_TRANSFORM_NONE; P2C_E_NULL for a missing camera or table, or no output at all. Then B = 0: nothing is launched. */
+enum { P2C_GENERATE_NOISE_ZERO = 0, P2C_GENERATE_NOISE_UNIFORM = 1 };
+enum { P2C_GENERATE_AUTO = 0, P2C_GENERATE_SEQUENTIAL = 1, P2C_GENERATE_FRAME_PARALLEL = 2 };
+#define P2C_GENERATE_MAX_T 65536
+#define P2C_GENERATE_FRAME_PARALLEL_MAX_FRAMES 8192
+P2C_API int p2c_carla_generate_fwd(int64_t seed, int32_t draw_stream, int64_t first_clip, int64_t B, int32_t T,
+                                   int32_t random_changes_each_frame, float max_change_rad, float max_world_rot_change_rad,
+                                   float max_initial_world_rot_change_rad, int32_t transform, int32_t noise, float noise_param,
+                                   const float *miss_prob, float near_zero, const float *camera, const float *ref_rel_loc,
+                                   const float *ref_rel_rot, float *frames, float *projection_2d, float *projection_2d_deformed,
+                                   float *projection_2d_transformed, float *projection_2d_shift, float *projection_2d_scale,
+                                   float *pose_changes, float *relative_pose_loc, float *relative_pose_rot,
+                                   float *absolute_pose_loc, float *absolute_pose_rot, float *world_loc, float *world_rot,
+                                   float *world_loc_changes, float *world_rot_changes, int32_t *skel_type, int32_t mapping,
+                                   int32_t max_blocks, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

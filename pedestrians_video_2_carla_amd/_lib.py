@@ -373,7 +373,13 @@ SYMBOLS = {
     'p2c_smpl_to_carla_fwd': (ctypes.c_int, [_vp, _vp, _i64] + [_vp] * 10 + [_i64, _i32, _vp]),
     'p2c_loc_to_carla_fwd': (ctypes.c_int, [_vp, _vp, _i64] + [_vp] * 9 + [_i64, _i32, _vp]),
     'p2c_carla_resample_fwd': (ctypes.c_int, [_vp] * 6 + [_i64, _i64, _i32, _i64, _i64, _i64, ctypes.c_double, _i32, _i32, _vp]),
+    'p2c_carla_generate_fwd': (ctypes.c_int, [_i64, _i32, _i64, _i64, _i32, _i32] + [ctypes.c_float] * 3 + [_i32, _i32, ctypes.c_float,
+                                              _fp, ctypes.c_float, _fp] + [_vp] * 18 + [_i32, _i32, _vp]),
 }
+
+P2C_GENERATE_NOISE = {'zero': 0, 'uniform': 1}
+P2C_GENERATE_MAPPING = {'auto': 0, 'sequential': 1, 'frame_parallel': 2}
+P2C_GENERATE_MAX_T, P2C_GENERATE_FRAME_PARALLEL_MAX_FRAMES = 65536, 8192
 
 _lib = None
 

@@ -299,6 +299,19 @@ struct HeadAcc {
   float sum2, cnt2, sum3;
 };
 
+// The pinhole projection of one joint (walker_control/p3d_pose_projection.py:115-152, camera :37-69): x the absolute location, p the
+// point in the camera's world, (u, v) the pixel, invZ = 1 / depth. One definition for frame_head and for K38 (p2c_generate.hip), whose
+// batches must carry the projection the pose head computes. D: anything with the cam_* fields.
+template <class D>
+__device__ __forceinline__ void project_joint(const D &d, V3 x, const World &W, V3 &p, float &invZ, float &u, float &v) {
+  V3 w = v3(x.y, -x.x, x.z);  // x @ p3d_2_world
+  p = W.on ? vmul(w, W.rot) + W.loc : w;
+  float Z = d.cam_dist - p.x;
+  invZ = frcp(Z);
+  u = d.cam_cx - d.cam_f * p.y * invZ;
+  v = d.cam_cy + d.cam_f * (p.z + d.cam_elev) * invZ;
+}
+
 enum { MODE_FWD = 0, MODE_FWD_MATERIALIZE = 1, MODE_BWD = 2, MODE_TRAIN = 3 };   // TRAIN = BWD that also sums the losses
 
 // 1 / (number of joints averaged into the hips or the neck point), as frame_head's backward multiplies by it. A descriptor type
@@ -318,12 +331,9 @@ __device__ __forceinline__ V3 frame_head(const D &d, const LaneCtx &L, int t, V3
   const size_t frame = (size_t)L.clip * d.T + t;
 
   // ---- projection --------------------------------------------------------------------------------------------------
-  V3 w = v3(x.y, -x.x, x.z);  // x @ p3d_2_world
-  V3 p = W.on ? vmul(w, W.rot) + W.loc : w;
-  float Z = d.cam_dist - p.x;
-  float invZ = frcp(Z);
-  float u = d.cam_cx - d.cam_f * p.y * invZ;
-  float v = d.cam_cy + d.cam_f * (p.z + d.cam_elev) * invZ;
+  V3 p;
+  float invZ, u, v;
+  project_joint(d, x, W, p, invZ, u, v);
   if (!L.active) { u = 0.f; v = 0.f; invZ = 0.f; }
 
   if constexpr (MAT) {

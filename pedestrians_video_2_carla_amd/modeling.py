@@ -9,7 +9,8 @@ wires a ``ModelCheckpoint(monitor='val_loss/primary', mode='min', save_top_k=1)`
   test     the checkpoint's weights; the validation set (which reproduces the monitor the checkpoint was chosen by) and the test set
   predict  ``trainer.predict`` over every ``--predict_sets`` entry -> ``dm.save_predictions`` (a subset ``load_subset`` reads back)
 
-Data modules: the synthetic CARLA-recorded one (no files) and the mixed modules over stored subsets under ``--subsets_dir``
+Data modules: the synthetic CARLA-recorded one (no files), ``Carla2D3D`` (the reference's infinite training set, generated on the
+device by K38; no files either) and the mixed modules over stored subsets under ``--subsets_dir``
 (``{subsets_dir}/{SourceDataModule}/{train,val,test}.hdf5|npz``). W&B and TensorBoard are out of scope: the log directory is
 ``{logs_dir}/{flow}/{data module}/{models...}/{version}``.
 """
@@ -36,11 +37,12 @@ def flow_modules() -> Dict[str, type]:
 
 
 def data_modules() -> Dict[str, type]:
+    from pedestrians_video_2_carla_amd.data.carla.carla_2d3d import Carla2D3DDataModule
     from pedestrians_video_2_carla_amd.data.carla.carla_recorded_synthetic import SyntheticCarlaRecordedDataModule
     from pedestrians_video_2_carla_amd.data.mixed.mixed_datamodule import (CarlaRecAMASSDataModule, JAADCarlaRecAMASSDataModule,
                                                                          JAADCarlaRecBenchmarkDataModule, JAADCarlaRecDataModule)
     mixed = [JAADCarlaRecDataModule, JAADCarlaRecBenchmarkDataModule, CarlaRecAMASSDataModule, JAADCarlaRecAMASSDataModule]
-    return {'SyntheticCarlaRecorded': SyntheticCarlaRecordedDataModule,
+    return {'SyntheticCarlaRecorded': SyntheticCarlaRecordedDataModule, 'Carla2D3D': Carla2D3DDataModule,
             **{cls.__name__.replace('DataModule', ''): cls for cls in mixed}}
 
 
@@ -111,6 +113,8 @@ def build_parser(args: List[str]) -> Tuple[argparse.ArgumentParser, type, type, 
     dm_cls, flow_cls, models_cls = setup_classes(program_args, parser, known)
     add_trainer_args(parser)
     add_data_args(parser)
+    if hasattr(dm_cls, 'add_data_specific_args'):
+        dm_cls.add_data_specific_args(parser)
     flow_cls.add_model_specific_args(parser)
     for model_cls in models_cls.values():
         model_cls.add_model_specific_args(parser)
