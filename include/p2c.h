@@ -1247,6 +1247,52 @@ P2C_API int p2c_carla_generate_fwd(int64_t seed, int32_t draw_stream, int64_t fi
                                    float *world_loc_changes, float *world_rot_changes, int32_t *skel_type, int32_t mapping,
                                    int32_t max_blocks, void *stream);
 
+/* ---- K39: CARLA rows smoothed along time in one launch (csrc/p2c_smooth.hip) ------------------------------------------------
+ * What takes the frame-to-frame jitter of per-frame predictions out of an animation before it is played; the reference has no
+ * such step. Definition: walker_control/smooth.py. N videos, each row (x, y, z, pitch, yaw, roll); rotations are filtered as the
+ * unit quaternions of p2c_carla_resample_fwd and written back through the row arithmetic of p2c_carla_pose_fwd. fp32, no backward.
+ *
+ * p2c_carla_smooth_gauss_fwd: a zero-phase weighted mean over 2R + 1 frames.
+ *   bones (N,S,J,6), root (N,S,6) or NULL: the source frames with global indices first_frame .. first_frame + S - 1.
+ *   out_bones (N,K,J,6), out_root (N,K,6) or NULL: output frames with global indices first_output .. first_output + K - 1.
+ *   weights (R + 1) on the device: weights[d] for a neighbour d frames away (the host's float32(exp(-d^2 / (2 sigma^2)))); not read
+ *     and may be NULL with R = 0.
+ *   last_frame: the global index of the video's last frame, or -1 while it is not known.
+ * Output frame t combines source frames max(0, t - R) .. min(t + R, last_frame): locations sum(w x) / sum(w), rotations the
+ * normalised sum of w q over the neighbours' quaternions, each negated when its dot product with the centre frame's is < 0; every
+ * sum in ascending frame order. R = 0 copies the rows bit for bit. A NaN in a source row reaches the outputs of that row within R
+ * frames and nothing else. A window is clamped into the given frames in the kernel, never followed outside them, and an output
+ * whose own frame is not given is NaN: the caller checks that every window lies inside (with last_frame = -1: up to t + R).
+ * A workgroup converts the rows of a tile's F + 2R source frames once into LDS (F <= 32; at most 64 KB) and forms the tile's
+ * output rows from there. A row's bits depend on its window's source rows and the table only: not on the tile, the grid, whether
+ * the root is asked for, or where a streaming caller cut the video. One writer per element, no atomics.
+ *
+ * p2c_carla_smooth_euro_fwd: the one-euro filter (Casiez et al.), causal, a lane per (video, row) walking its T frames.
+ *   bones (N,T,J,6), root (N,T,6) or NULL -> out_bones, out_root of the same shapes.
+ *   state_bones (N,J,12), state_root (N,12): per row (x^ 3, v^ 3, q^ 4 w first, w^ 1, 0). has_state = 1: read before frame 0 (the
+ *     frames continue a video); has_state = 0: frame 0 starts the state (x^ = x, q^ = the row's quaternion, v^ = w^ = 0) and its
+ *     row is copied bit for bit. Where a state pointer is given the state after frame T - 1 is written there.
+ *   With alpha(fc) = 1 / (1 + fps / (2 pi fc)): v = (x - x^) fps, v^ += alpha(d_cutoff) (v - v^), x^ += alpha(min_cutoff +
+ *   beta_loc |v^|) (x - x^); q the row's quaternion on q^'s hemisphere, d = min(q^ . q, 1) by comparison, w = 2 acos(d) fps,
+ *   w^ += alpha(d_cutoff) (w - w^), q^ = normalised slerp(q^, q, alpha(min_cutoff + beta_rot w^)) with lerp weights above
+ *   d = 0.99999. The parameters are used at their fp32 values; alpha(d_cutoff) and fps / 2 pi are formed in fp64 and
+ *   rounded once. A NaN row poisons its own chain from that frame on and nothing else. No LDS, no atomics.
+ *
+ * max_blocks  0: the kernel's own grid cap; > 0 lowers it (workgroups stride over tiles, lanes over chains).
+ * In this order, before anything is launched: P2C_E_SHAPE for negative sizes or indices (last_frame < -1), J < 1, max_blocks < 0,
+ * R outside [0, P2C_SMOOTH_MAX_RADIUS], N K (J + 1) or N S (J + 1) > 2^40, first_frame + S or first_output + K > 2^40, outputs
+ * asked of no frames (S = 0 with N, K > 0), has_state other than 0 / 1, fps, min_cutoff or d_cutoff not finite or not positive
+ * (as given or as fp32), a beta that is negative or not finite; P2C_E_NULL for a missing bones / out_bones, root without out_root
+ * or the reverse, weights missing with R > 0, a state missing where it is read. Then N = 0 or K = 0 (T = 0): nothing is launched. */
+#define P2C_SMOOTH_MAX_RADIUS 32
+P2C_API int p2c_carla_smooth_gauss_fwd(const float *bones, const float *root, float *out_bones, float *out_root,
+                                       const float *weights, int64_t N, int64_t S, int32_t J, int64_t K, int64_t first_frame,
+                                       int64_t first_output, int64_t last_frame, int32_t R, int32_t max_blocks, void *stream);
+P2C_API int p2c_carla_smooth_euro_fwd(const float *bones, const float *root, float *state_bones, float *state_root,
+                                      float *out_bones, float *out_root, int64_t N, int64_t T, int32_t J, int32_t has_state,
+                                      double fps, double min_cutoff, double beta_loc, double beta_rot, double d_cutoff,
+                                      int32_t max_blocks, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -375,7 +375,11 @@ SYMBOLS = {
     'p2c_carla_resample_fwd': (ctypes.c_int, [_vp] * 6 + [_i64, _i64, _i32, _i64, _i64, _i64, ctypes.c_double, _i32, _i32, _vp]),
     'p2c_carla_generate_fwd': (ctypes.c_int, [_i64, _i32, _i64, _i64, _i32, _i32] + [ctypes.c_float] * 3 + [_i32, _i32, ctypes.c_float,
                                               _fp, ctypes.c_float, _fp] + [_vp] * 18 + [_i32, _i32, _vp]),
+    'p2c_carla_smooth_gauss_fwd': (ctypes.c_int, [_vp] * 5 + [_i64, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _vp]),
+    'p2c_carla_smooth_euro_fwd': (ctypes.c_int, [_vp] * 6 + [_i64, _i64, _i32, _i32] + [ctypes.c_double] * 5 + [_i32, _vp]),
 }
+
+P2C_SMOOTH_MAX_RADIUS = 32
 
 P2C_GENERATE_NOISE = {'zero': 0, 'uniform': 1}
 P2C_GENERATE_MAPPING = {'auto': 0, 'sequential': 1, 'frame_parallel': 2}

@@ -1,4 +1,5 @@
-// p2c_carla_dev.h -- shared by p2c_carla_pose.hip (K30) and p2c_lift.hip (K32): carla_row; by p2c_smpl.hip (K35) and p2c_ik.hip (K36): all of it.
+// p2c_carla_dev.h -- shared by p2c_carla_pose.hip (K30) and p2c_lift.hip (K32): carla_row; by p2c_resample.hip (K37) and p2c_smooth.hip (K39):
+// carla_row and row_quat; by p2c_smpl.hip (K35) and p2c_ik.hip (K36): all of it.
 // The arithmetic of one exported CARLA row (definitions and reference citations: p2c_carla_pose.hip) and the frame front end, rows
 // tail and argument checks of the per-frame converters.
 #pragma once
@@ -23,6 +24,19 @@ __device__ __forceinline__ void carla_row(float x, float y, float z, float r00, 
   const float e2 = atan2f(-r01, r00);
   o[0] = x, o[1] = y, o[2] = -z;
   o[3] = -(e1 * kDeg), o[4] = -(e2 * kDeg), o[5] = -(e0 * kDeg);
+}
+
+// rows (x, y, z, pitch, yaw, roll) -> unit quaternion (w, x, y, z) of Rx(e0) Ry(e1) Rz(e2)
+__device__ __forceinline__ void row_quat(float pitch, float yaw, float roll, float &w, float &x, float &y, float &z) {
+  float s0, c0, s1, c1, s2, c2;
+  sincosf(-roll * kRad * 0.5f, &s0, &c0);
+  sincosf(-pitch * kRad * 0.5f, &s1, &c1);
+  sincosf(-yaw * kRad * 0.5f, &s2, &c2);
+  const float w1 = c0 * c1, x1 = s0 * c1, y1 = c0 * s1, z1 = s0 * s1;   // qx qy
+  w = w1 * c2 - z1 * s2;
+  x = x1 * c2 + y1 * s2;
+  y = y1 * c2 - x1 * s2;
+  z = w1 * s2 + z1 * c2;
 }
 
 // ---- a frame per 32-lane group (K35, K36): lanes 0..25 the bones in CARLA_SKELETON (= DFS) order, lane 26 the spare, the rest idle

@@ -26,12 +26,12 @@
 #include "../../include/p2c.h"
 #include "p2c_host.h"
 
-#include "p2c_carla_dev.h"   // kRad, carla_row
+#include "p2c_carla_dev.h"   // carla_row, row_quat
 
 namespace p2c_resample {
 
 using p2c_carla::carla_row;
-using p2c_carla::kRad;
+using p2c_carla::row_quat;
 
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;   // 8 workgroups per CU on 256 CUs
@@ -53,19 +53,6 @@ __device__ __forceinline__ void divmod(int64_t a, int64_t b, int64_t &q, int64_t
   } else {
     q = a / b, r = a - q * b;
   }
-}
-
-// rows (x, y, z, pitch, yaw, roll) -> unit quaternion (w, x, y, z) of Rx(e0) Ry(e1) Rz(e2)
-__device__ __forceinline__ void row_quat(float pitch, float yaw, float roll, float &w, float &x, float &y, float &z) {
-  float s0, c0, s1, c1, s2, c2;
-  sincosf(-roll * kRad * 0.5f, &s0, &c0);
-  sincosf(-pitch * kRad * 0.5f, &s1, &c1);
-  sincosf(-yaw * kRad * 0.5f, &s2, &c2);
-  const float w1 = c0 * c1, x1 = s0 * c1, y1 = c0 * s1, z1 = s0 * s1;   // qx qy
-  w = w1 * c2 - z1 * s2;
-  x = x1 * c2 + y1 * s2;
-  y = y1 * c2 - x1 * s2;
-  z = w1 * s2 + z1 * c2;
 }
 
 __global__ __launch_bounds__(kThreads) void carla_resample_kernel(Args a) {

@@ -3732,6 +3732,96 @@ def resample_carla_rows(bones: Tensor, root: Optional[Tensor] = None, *, src_fps
     return out_b, out_r
 
 
+# ---- K39: CARLA rows smoothed along time (csrc/p2c_smooth.hip) -----------------------------------------------------------------
+def smooth_framework() -> bool:
+    """P2C_SMOOTH_FRAMEWORK=1: ``smooth_carla_rows`` runs its tensor definition on the device (the comparison arm of
+    tools/bench_smooth.py)."""
+    return os.environ.get('P2C_SMOOTH_FRAMEWORK', '0') == '1'
+
+
+_SMOOTH_TABLES: Dict[Tuple, Tensor] = {}
+
+
+def _smooth_table(sigma: float, R: int, device) -> Tensor:
+    """The gaussian weight table of (sigma, R) on ``device``, formed once."""
+    from pedestrians_video_2_carla_amd.walker_control import smooth as sm
+    key = (sigma, R, str(device))
+    if key not in _SMOOTH_TABLES:
+        if len(_SMOOTH_TABLES) >= 64:
+            _SMOOTH_TABLES.clear()
+        _SMOOTH_TABLES[key] = sm.gauss_table(sigma, R).to(device)
+    return _SMOOTH_TABLES[key]
+
+
+@torch.no_grad()
+def smooth_carla_rows(bones: Tensor, root: Optional[Tensor] = None, *, mode: str, sigma=None, radius=None, fps=None,
+                      min_cutoff=1.0, beta_loc=0.0, beta_rot=0.0, d_cutoff=1.0, state=None, first_frame: int = 0,
+                      first_output: int = 0, count: Optional[int] = None, last_frame: Optional[int] = None,
+                      max_blocks: int = 0) -> Tuple[Tensor, Optional[Tensor], Optional[Tuple]]:
+    """Exported rows smoothed along time (definition: ``walker_control/smooth.py``). ``bones`` (N,T,J,6) and ``root`` (N,T,6) or
+    None, rows of (x, y, z, pitch, yaw, roll) -> ``(bones, root or None, state or None)``; rotations are filtered as quaternions.
+    ``mode='gaussian'`` (``sigma`` in frames, ``radius`` R <= 32, default ``ceil(3 sigma)``): output frame t is the weighted mean
+    of source frames ``max(0, t - R) .. min(t + R, last_frame)``. ``bones[:, 0]`` is global source frame ``first_frame``,
+    ``out[:, 0]`` global output ``first_output``; ``last_frame`` is the video's last global index (None: the last frame given;
+    -1: not known yet, every window must then lie inside the given frames); ``count`` outputs are returned (None: all that can
+    be formed). A window that reads a frame that is not given raises. R = 0 or sigma = 0 copies the rows; the state is None.
+    ``mode='one_euro'`` (``fps``, ``min_cutoff``, ``beta_loc``, ``beta_rot``, ``d_cutoff``): the causal one-euro filter over the T
+    frames; ``state`` = ``(bones (N,J,12), root (N,12) or None)`` continues a video (None: frame 0 starts one and is copied),
+    and the state after the last frame is returned; the given one is left as it was. Any J >= 1; views are made contiguous;
+    nothing is recorded for autograd. fp32 device tensors outside autocast take K39 (one launch for bones and root); host
+    tensors, fp64, other dtypes and ``P2C_SMOOTH_FRAMEWORK=1`` take the tensor definition. ``max_blocks`` lowers the kernel's
+    grid cap (tests)."""
+    from pedestrians_video_2_carla_amd.walker_control import resample as rs, smooth as sm
+    sm.check_mode(mode)
+    rs.check_rows(bones, root, None, 'smooth_carla_rows')
+    N, T, n_joints, _ = bones.shape
+    f32 = dict(dtype=torch.float32, device=bones.device)
+    if mode == 'one_euro':
+        params = sm.euro_params(fps, min_cutoff, beta_loc, beta_rot, d_cutoff)
+        sb, sr = sm.check_state(bones, root, state)
+        if T == 0:
+            return bones.detach().clone(), (root.detach().clone() if root is not None else None), state
+        given = [t for t in (bones, root, sb, sr) if t is not None]
+        if not _carla_kernel_ok(*given) or smooth_framework():
+            return sm.euro_rows(bones, root, sb, sr, params)
+        src_b, src_r = (t.detach().contiguous() if t is not None else None for t in (bones, root))
+        new_b = sb.detach().clone().contiguous() if sb is not None else torch.empty((N, n_joints, sm.STATE), **f32)
+        new_r = None
+        if root is not None:
+            new_r = sr.detach().clone().contiguous() if sr is not None else torch.empty((N, sm.STATE), **f32)
+        out_b = torch.empty((N, T, n_joints, 6), **f32)
+        out_r = torch.empty((N, T, 6), **f32) if root is not None else None
+        if N > 0:
+            with torch.cuda.device(bones.device):
+                _lib.check(_lib.lib().p2c_carla_smooth_euro_fwd(
+                    src_b.data_ptr(), _ptr(src_r), new_b.data_ptr(), _ptr(new_r), out_b.data_ptr(), _ptr(out_r), N, T, n_joints,
+                    int(sb is not None), params['fps'], params['min_cutoff'], params['beta_loc'], params['beta_rot'],
+                    params['d_cutoff'], int(max_blocks), _stream()), 'p2c_carla_smooth_euro_fwd')
+        return out_b, out_r, (new_b, new_r)
+    sigma, R = sm.gauss_params(sigma, radius)
+    first_frame, first_output = int(first_frame), int(first_output)
+    last_frame = first_frame + T - 1 if last_frame is None else int(last_frame)
+    if count is None:
+        count = max((last_frame if last_frame >= 0 else first_frame + T - 1 - R) - first_output + 1, 0)
+    count = int(count)
+    sm.check_gauss_span(first_output, count, R, first_frame, T, last_frame, 'smooth_carla_rows')
+    given = [t for t in (bones, root) if t is not None]
+    if not _carla_kernel_ok(*given) or smooth_framework():
+        return (*sm.gauss_rows(bones, root, _smooth_table(sigma, R, bones.device), R, first_frame, first_output, count, last_frame), None)
+    src_b, src_r = (t.detach().contiguous() if t is not None else None for t in (bones, root))
+    out_b = torch.empty((N, count, n_joints, 6), **f32)
+    out_r = torch.empty((N, count, 6), **f32) if root is not None else None
+    if N == 0 or count == 0:
+        return out_b, out_r, None
+    table = _smooth_table(sigma, R, bones.device)
+    with torch.cuda.device(bones.device):
+        _lib.check(_lib.lib().p2c_carla_smooth_gauss_fwd(src_b.data_ptr(), _ptr(src_r), out_b.data_ptr(), _ptr(out_r),
+                                                         table.data_ptr(), N, T, n_joints, count, first_frame, first_output,
+                                                         last_frame, R, int(max_blocks), _stream()),
+                   'p2c_carla_smooth_gauss_fwd')
+    return out_b, out_r, None
+
+
 # ---- K33: decoded video clips -> the pose-estimation flow's input frames (csrc/p2c_frames.hip) ---------------------------------
 FRAMES_MAX_TARGET = 1024             # the largest target size K33 is dispatched for
 

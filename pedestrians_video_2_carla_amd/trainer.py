@@ -829,7 +829,7 @@ class Trainer:
         finally:
             flow.train(was_training)
 
-    def predict_carla(self, flow, batches: Iterable, ik: bool = False, src_fps=None, out_fps=None) -> List:
+    def predict_carla(self, flow, batches: Iterable, ik: bool = False, src_fps=None, out_fps=None, smooth=None) -> List:
         """The predict loop for a CARLA player: per batch ``(bones (B,T,26,6), root (B,T,6), meta)``, the rows
         ``export_clips(flow.predict_step(batch))`` would give, left on the batch's device. A LinearAE flow takes one launch per
         batch (K32, ``walker_control.carla_lifter.CarlaLifter``); other movements models the composed path. A movements model
@@ -837,7 +837,9 @@ class Trainer:
         goes through ``walker_control.location_retargeter.LocationRetargeter`` instead: model -> pose head -> the rotations
         fitted to the predicted locations (K36, one launch per batch). ``src_fps`` and ``out_fps``, given together: every
         clip's rows are resampled from the one rate to the other where they are (``CarlaResampler.resample``, K37: one more
-        launch per batch), so T becomes the clip's output count. Eval mode, no gradients, the flow's train / eval mode is
+        launch per batch), so T becomes the clip's output count. ``smooth``: a ``CarlaSmoother`` or a dict of its arguments; every
+        clip's rows are smoothed along time as a video of its own (``CarlaSmoother.smooth``, K39: one more launch per batch)
+        before any resampling (a dict for ``one_euro`` without ``fps`` takes ``src_fps``). Eval mode, no gradients, the flow's train / eval mode is
         put back afterwards."""
         from pedestrians_video_2_carla_amd.walker_control.carla_lifter import CarlaLifter
         if (src_fps is None) != (out_fps is None):
@@ -847,6 +849,10 @@ class Trainer:
         else:
             from pedestrians_video_2_carla_amd.walker_control.resample import CarlaResampler
             rate = CarlaResampler(src_fps, out_fps).resample
+        if smooth is not None:
+            from pedestrians_video_2_carla_amd.walker_control.smooth import as_smoother
+            smoother, resample = as_smoother(smooth, src_fps), rate
+            rate = lambda bones, root: resample(*smoother.smooth(bones, root))     # noqa: E731
         lifter = CarlaLifter(flow)
         was_training = flow.training
         flow.eval()

@@ -150,7 +150,12 @@ def interpolate_rows(a: Tensor, b: Tensor, frac: Tensor) -> Tensor:
     wa = torch.where(lerp, 1.0 - f, torch.sin((1.0 - f) * theta) * inv)
     wb = torch.where(lerp, f + torch.zeros_like(d), torch.sin(f * theta) * inv)
     q = wa * qa + wb * qb
-    q = q / torch.sqrt((q * q).sum(-1, keepdim=True))
+    return _quat_rows(loc, q / torch.sqrt((q * q).sum(-1, keepdim=True)))
+
+
+def _quat_rows(loc: Tensor, q: Tensor) -> Tensor:
+    """Locations (...,3) and unit quaternions (...,4) -> rows (...,6), read back through the five matrix entries
+    ``ops.carla_pose_export`` reads (shared with ``walker_control/smooth.py``)."""
     w, x, y, z = q.unbind(-1)
     r00, r01, r02 = 1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)
     r12, r22 = 2 * (y * z - w * x), 1 - 2 * (x * x + y * y)
