@@ -507,7 +507,10 @@ using namespace p2c_lstm;
 
 static int check(const p2c_lstm_desc *d, Args &a) {
   if (!d || !d->w_hh) return P2C_E_NULL;
-  if (d->T < 0 || d->B < 0 || d->B > (1 << 20)) return P2C_E_SHAPE;   // buffer offsets: (B + 16) * 4H * 4 bytes < 2^31
+  // buffer offsets are 32-bit: a row of step t starts at b * 4H * 4 bytes, 2 KB apart at the widest layer (H = 128), so the rows of
+  // real sequences (b < B <= 2^20) start below 2^31. The padding lanes of the last tile (b < B + 16) may pass 2^31 there: as the
+  // unsigned offset the buffer instruction compares with num_records (B * 4H * 4 <= 2^31) they stay out of range.
+  if (d->T < 0 || d->B < 0 || d->B > (1 << 20)) return P2C_E_SHAPE;
   if (d->H != 16 && d->H != 32 && d->H != 48 && d->H != 64 && d->H != 96 && d->H != 128) return P2C_E_SHAPE;
   a = Args{};
   a.gx = d->gx, a.h0 = d->h0, a.c0 = d->c0, a.w_hh = d->w_hh, a.out = d->out, a.hT = d->hT, a.cT = d->cT;
@@ -567,6 +570,7 @@ extern "C" int p2c_lstm_rec_fwd(const p2c_lstm_desc *d, void *stream) {
   if (rc) return rc;
   if (!a.gx || !a.out) return P2C_E_NULL;
   if (a.B == 0) return 0;
+  if (a.T == 0) a.gx = nullptr;   // the kernels request step 0's rows ahead of the loop: gx has none, a NULL tensor has no records
   if (use_narrow(a.B)) {
     const dim3 grid((unsigned)((a.B + NS - 1) / NS));
     P2C_LSTM_DISPATCH(lstm_rec_fwd_narrow_kernel, false)

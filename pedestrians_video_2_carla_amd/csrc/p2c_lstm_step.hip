@@ -176,6 +176,15 @@ static int check_steps(const p2c_lstm_desc *d, Args &a) {
   return 0;
 }
 
+// T = 0 (p2c.h): no step runs, so the final state is the initial one and the gradient of the initial state is that of the final one --
+// copied on the stream, or zero-filled where the source is NULL.
+static int pass_state(float *dst, const float *src, const Args &a, hipStream_t stream) {
+  if (!dst || dst == src) return 0;
+  const size_t bytes = (size_t)a.B * a.H * sizeof(float);
+  const hipError_t e = src ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream) : hipMemsetAsync(dst, 0, bytes, stream);
+  return e == hipSuccess ? 0 : (int)e;
+}
+
 extern "C" int64_t p2c_lstm_steps_workspace_floats(int32_t B, int32_t H) { return workspace_floats(B, H); }
 
 extern "C" int p2c_lstm_steps_fwd(const p2c_lstm_desc *d, void *stream) {
@@ -184,6 +193,10 @@ extern "C" int p2c_lstm_steps_fwd(const p2c_lstm_desc *d, void *stream) {
   if (rc) return rc;
   if (!a.gx || !a.out || !a.acts || !a.cs) return P2C_E_NULL;   // cs carries the cell state from one launch to the next
   if (a.B == 0) return 0;
+  if (a.T == 0) {
+    if (int e = pass_state(a.hT, a.h0, a, (hipStream_t)stream)) return e;
+    return pass_state(a.cT, a.c0, a, (hipStream_t)stream);
+  }
   for (int t = 0; t < a.T; ++t) hipLaunchKernelGGL(lstm_step_fwd_kernel, steps_grid(a.B, a.H), dim3(NT), 0, (hipStream_t)stream, a, t);
   return p2c_host::launch_status();
 }
@@ -195,7 +208,11 @@ extern "C" int p2c_lstm_steps_bwd(const p2c_lstm_desc *d, float *workspace, void
   if (!a.acts || !a.cs || !a.g_gx) return P2C_E_NULL;
   if (a.T > 1 && !workspace) return P2C_E_NULL;
   a.dc = workspace;
-  if (a.B == 0 || a.T == 0) return 0;
+  if (a.B == 0) return 0;
+  if (a.T == 0) {
+    if (int e = pass_state(a.g_h0, a.g_hT, a, (hipStream_t)stream)) return e;
+    return pass_state(a.g_c0, a.g_cT, a, (hipStream_t)stream);
+  }
   for (int t = a.T - 1; t >= 0; --t) hipLaunchKernelGGL(lstm_step_bwd_kernel, steps_grid(a.B, a.H), dim3(NT), 0, (hipStream_t)stream, a, t);
   if (a.g_h0) hipLaunchKernelGGL(lstm_step_bwd_kernel, steps_grid(a.B, a.H), dim3(NT), 0, (hipStream_t)stream, a, -1);
   return p2c_host::launch_status();

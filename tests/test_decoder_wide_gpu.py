@@ -67,11 +67,13 @@ def _loop_reference(T, B, O, with_drop):
 
 @gpu
 @pytest.mark.parametrize('T,B,O,with_drop', [(1, 1, 65, False), (16, 37, 156, True), (5, 16, 160, False), (16, 130, 78, True),
-                                             (3, 5, 97, False)])
+                                             (3, 5, 97, False)] + [
+    (T, B, O, with_drop) for T, O in ((3, 66), (5, 79), (4, 80), (5, 81), (2, 159)) for B, with_drop in ((5, False), (17, True))])
 def test_wide_decoder_loop_matches_the_per_step_formula(T, B, O, with_drop, rec_tile):
     """K7c against the reference loop written out in fp64: out_t = fc(cell1(cell0(x_t))) with the frozen encoder state; output and
     all eight gradients. 65: first width past the 64-feature kernels; 97: one feature into a new 16-block; 156: a multiple of 4, not
-    of 16; 160: full. B = 1, 5, 37, 130 leave a ragged clip tile, 16 is an exact one."""
+    of 16; 160: full. B = 1, 5, 37, 130 leave a ragged clip tile, 16 is an exact one. 79, 80, 81: either side of the O <= 80 dispatch
+    boundary; 66 and 159: next to 65 and 160 from the inside; each with and without the mask at B = 5 and 17."""
     from pedestrians_video_2_carla_amd import ops
     d = dev()
     P, drop, up, ref, grads = _loop_reference(T, B, O, with_drop)

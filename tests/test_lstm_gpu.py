@@ -230,9 +230,12 @@ def test_no_cpu_fallback():
                        None, None)
 
 
-@pytest.mark.parametrize('T,B,O,with_drop', [(1, 1, 52, False), (16, 37, 52, True), (5, 16, 64, False), (16, 130, 12, True)])
+@pytest.mark.parametrize('T,B,O,with_drop', [(1, 1, 52, False), (16, 37, 52, True), (5, 16, 64, False), (16, 130, 12, True)] + [
+    (T, B, O, with_drop) for T, O in ((2, 1), (3, 3), (5, 50), (4, 51), (5, 53), (3, 63)) for B, with_drop in ((5, False), (17, True))])
 def test_decoder_loop_matches_the_per_step_formula(T, B, O, with_drop):
-    """K7c against the reference loop written out in fp64: out_t = fc(cell1(cell0(x_t))) with the frozen encoder state."""
+    """K7c against the reference loop written out in fp64: out_t = fc(cell1(cell0(x_t))) with the frozen encoder state. The widths
+    next to the dispatch boundaries of p2c_decoder_fwd / _bwd (O <= 52, <= 64) from either side and the ones that are no multiple
+    of 4 -- 1, 3, 50, 51, 53, 63 -- run with and without the mask at B = 5 and 17 (a ragged tile on both tilings)."""
     from pedestrians_video_2_carla_amd import ops
     d = dev()
     H = 64
