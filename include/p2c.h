@@ -1295,6 +1295,46 @@ P2C_API int p2c_carla_smooth_euro_fwd(const float *bones, const float *root, flo
                                       double fps, double min_cutoff, double beta_loc, double beta_rot, double d_cutoff,
                                       int32_t max_blocks, void *stream);
 
+/* ---- K40: root motion of a CARLA animation from its planted feet (csrc/p2c_root_motion.hip) ---------------------------------
+ * Every exporter takes the root row from world_loc, which the only trajectory model (ZeroTrajectory) leaves at zero: a played
+ * animation walks on the spot. This stage puts the displacement back: the contact joint that is lowest over two neighbouring
+ * frames must not move in the world, so the actor moves the other way. Definition: walker_control/root_motion.py. fp32, no backward.
+ *   bones (N,T,26,6), root (N,T,6) or NULL (all-zero root rows): frames first_frame .. first_frame + T - 1 of N videos.
+ *   Per frame g: (l, R) of every row as p2c_carla_pose_inv forms them, forward kinematics over the 26-bone tree (row vectors), the
+ *   actor as one more parent: p_k = x_{C_k} W + r for C = bones (18, 19, 23, 24) (foot R, toe R, foot L, toe L); h_k = -p_k[2].
+ *   g >= 1: m_k = max(h_k(g - 1), h_k(g)); s = the smallest k with minimal m_k; d = p_s(g - 1)[0:2] - p_s(g)[0:2];
+ *     step(g) = rint(d * 2^10) (half to even) as two int32; contact(g) = s. A non-finite value among the eight heights or the four
+ *     coordinates read, or |d * 2^10| >= 2^31: step(g) = (0, 0), contact(g) = -1.
+ *   g == 0: step = (0, 0), contact = argmin_k h_k(0), -1 when a height is not finite.
+ *   S(g) = S(g - 1) + step(g) in int64, S(-1) = 0: an integer sum, exact and independent of mapping, grid, tiling and cuts.
+ *   out_root (N,T,6): x = fp32(fp64(x) + S_x(g) 2^-10), y likewise; z unchanged, or with has_ground = 1 z + (fp32(ground) - min_k
+ *     h_k(g)) in fp32 (NaN when a height of the frame is not finite); the three angles bit for bit. The bones are not rewritten.
+ *   out_steps (N,T,2) int32, out_contact (N,T) int8: NULL or given; what is written to an output does not depend on the others.
+ *   state_in_offset (N,2) int64 + state_in_points (N,4,3): S(first_frame - 1) and the four p_k of frame first_frame - 1, both or
+ *     neither; required and read with first_frame > 0, not read with first_frame = 0 (nothing lies before a video's first frame).
+ *   state_out_offset + state_out_points: both or neither; S and the p_k of the last frame given.
+ *   mapping  P2C_ROOT_MOTION_PER_VIDEO: a workgroup per video walks its tiles of P2C_ROOT_MOTION_TILE frames in order, one launch;
+ *     P2C_ROOT_MOTION_FRAME_PARALLEL: a workgroup per (video, tile) in two launches (steps and tile totals to the workspace, then
+ *     the rows); P2C_ROOT_MOTION_AUTO: by size. All give the same bits.
+ *   workspace  p2c_carla_root_motion_workspace(N, T, mapping) bytes on the device, 16-byte aligned (0: not used, may be NULL);
+ *     every word that is read was written by the same call.
+ *   max_blocks  0: the kernels' own grid cap; > 0 lowers it (workgroups stride over videos, or over tiles).
+ * One writer per element, no atomics. In this order, before anything is launched: P2C_E_SHAPE for negative sizes or first_frame,
+ * N, T or first_frame + T > 2^40, N T 27 > 2^40, max_blocks < 0, has_ground other than 0 / 1, a ground that is not finite (as given
+ * or as fp32); P2C_E_ENUM for another mapping; P2C_E_NULL for a missing bones / out_root, one half of a state pair, first_frame > 0
+ * without state_in, a missing workspace where the mapping uses one. Then N = 0 or T = 0: nothing is launched.
+ * p2c_carla_root_motion_tile: P2C_ROOT_MOTION_TILE. p2c_carla_root_motion_workspace: the bytes, or -1 for sizes or a mapping the
+ * entry point refuses. */
+enum { P2C_ROOT_MOTION_AUTO = 0, P2C_ROOT_MOTION_PER_VIDEO = 1, P2C_ROOT_MOTION_FRAME_PARALLEL = 2 };
+#define P2C_ROOT_MOTION_TILE 128
+P2C_API int32_t p2c_carla_root_motion_tile(void);
+P2C_API int64_t p2c_carla_root_motion_workspace(int64_t N, int64_t T, int32_t mapping);
+P2C_API int p2c_carla_root_motion_fwd(const float *bones, const float *root, const int64_t *state_in_offset,
+                                      const float *state_in_points, float *out_root, int32_t *out_steps, int8_t *out_contact,
+                                      int64_t *state_out_offset, float *state_out_points, int64_t N, int64_t T,
+                                      int64_t first_frame, double ground, int32_t has_ground, int32_t mapping,
+                                      int32_t max_blocks, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

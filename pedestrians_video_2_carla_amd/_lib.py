@@ -377,7 +377,12 @@ SYMBOLS = {
                                               _fp, ctypes.c_float, _fp] + [_vp] * 18 + [_i32, _i32, _vp]),
     'p2c_carla_smooth_gauss_fwd': (ctypes.c_int, [_vp] * 5 + [_i64, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _vp]),
     'p2c_carla_smooth_euro_fwd': (ctypes.c_int, [_vp] * 6 + [_i64, _i64, _i32, _i32] + [ctypes.c_double] * 5 + [_i32, _vp]),
+    'p2c_carla_root_motion_tile': (_i32, []),
+    'p2c_carla_root_motion_workspace': (_i64, [_i64, _i64, _i32]),
+    'p2c_carla_root_motion_fwd': (ctypes.c_int, [_vp] * 9 + [_i64, _i64, _i64, ctypes.c_double, _i32, _i32, _i32, _vp, _vp]),
 }
+
+P2C_ROOT_MOTION_MAPPING = {'auto': 0, 'per_video': 1, 'frame_parallel': 2}
 
 P2C_SMOOTH_MAX_RADIUS = 32
 

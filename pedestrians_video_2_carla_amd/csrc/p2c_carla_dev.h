@@ -1,5 +1,6 @@
 // p2c_carla_dev.h -- shared by p2c_carla_pose.hip (K30) and p2c_lift.hip (K32): carla_row; by p2c_resample.hip (K37) and p2c_smooth.hip (K39):
-// carla_row and row_quat; by p2c_smpl.hip (K35) and p2c_ik.hip (K36): all of it.
+// carla_row and row_quat; by p2c_smpl.hip (K35) and p2c_ik.hip (K36): all of it; by p2c_root_motion.hip (K40): row_pose (K30's too) and
+// the frame front end.
 // The arithmetic of one exported CARLA row (definitions and reference citations: p2c_carla_pose.hip) and the frame front end, rows
 // tail and argument checks of the per-frame converters.
 #pragma once
@@ -24,6 +25,25 @@ __device__ __forceinline__ void carla_row(float x, float y, float z, float r00, 
   const float e2 = atan2f(-r01, r00);
   o[0] = x, o[1] = y, o[2] = -z;
   o[3] = -(e1 * kDeg), o[4] = -(e2 * kDeg), o[5] = -(e0 * kDeg);
+}
+
+// row (x, y, z, pitch, yaw, roll) -> l[0..2] = (x, y, -z), r[0..8] = Rx(a0) Ry(a1) Rz(a2) row-major, (a0, a1, a2) = rad(-roll, -pitch,
+// -yaw): K30's inverse (p2c_carla_pose.hip) and the frame phase of K40 (p2c_root_motion.hip)
+__device__ __forceinline__ void row_pose(float x, float y, float z, float pitch, float yaw, float roll, float *l, float *r) {
+  float s0, c0, s1, c1, s2, c2;
+  sincosf(-roll * kRad, &s0, &c0);
+  sincosf(-pitch * kRad, &s1, &c1);
+  sincosf(-yaw * kRad, &s2, &c2);
+  l[0] = x, l[1] = y, l[2] = -z;
+  r[0] = c1 * c2;
+  r[1] = -(c1 * s2);
+  r[2] = s1;
+  r[3] = c0 * s2 + (s0 * s1) * c2;
+  r[4] = c0 * c2 - (s0 * s1) * s2;
+  r[5] = -(s0 * c1);
+  r[6] = s0 * s2 - (c0 * s1) * c2;
+  r[7] = s0 * c2 + (c0 * s1) * s2;
+  r[8] = c0 * c1;
 }
 
 // rows (x, y, z, pitch, yaw, roll) -> unit quaternion (w, x, y, z) of Rx(e0) Ry(e1) Rz(e2)

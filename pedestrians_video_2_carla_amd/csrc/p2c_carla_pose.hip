@@ -29,7 +29,7 @@
 #include "../../include/p2c.h"
 #include "p2c_host.h"
 
-#include "p2c_carla_dev.h"   // kDeg, kRad, clamp_unit, carla_row: shared with K32 (p2c_lift.hip)
+#include "p2c_carla_dev.h"   // kDeg, kRad, clamp_unit, carla_row: shared with K32 (p2c_lift.hip); row_pose: with K40 (p2c_root_motion.hip)
 
 namespace p2c_carla {
 
@@ -66,21 +66,7 @@ __global__ __launch_bounds__(kThreads) void carla_pose_inv_kernel(InvArgs a) {
   for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < a.n_bones; e += step) {
     const float *b = a.bones + e * 6;
     const float x = b[0], y = b[1], z = b[2], pitch = b[3], yaw = b[4], roll = b[5];
-    float s0, c0, s1, c1, s2, c2;
-    sincosf(-roll * kRad, &s0, &c0);
-    sincosf(-pitch * kRad, &s1, &c1);
-    sincosf(-yaw * kRad, &s2, &c2);
-    float *l = a.loc + e * 3, *r = a.rot + e * 9;
-    l[0] = x, l[1] = y, l[2] = -z;
-    r[0] = c1 * c2;
-    r[1] = -(c1 * s2);
-    r[2] = s1;
-    r[3] = c0 * s2 + (s0 * s1) * c2;
-    r[4] = c0 * c2 - (s0 * s1) * s2;
-    r[5] = -(s0 * c1);
-    r[6] = s0 * s2 - (c0 * s1) * c2;
-    r[7] = s0 * c2 + (c0 * s1) * s2;
-    r[8] = c0 * c1;
+    row_pose(x, y, z, pitch, yaw, roll, a.loc + e * 3, a.rot + e * 9);
   }
 }
 

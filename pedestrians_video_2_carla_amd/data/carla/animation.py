@@ -3,7 +3,8 @@
 One ``.npz`` with ``bones`` (N,T,J,6) and ``root`` (N,T,6) -- rows of (x, y, z, pitch, yaw, roll), metres and degrees, CARLA's
 axes, see ``ops.carla_pose_export`` -- ``bone_names`` (J), ``age`` / ``gender`` (N: which walker blueprint a clip belongs to)
 and ``fps``. Playing it needs a CARLA server and is not part of this package. ``resample_carla_animation`` rewrites a file at
-another rate (K37), ``smooth_carla_animation`` smoothed along time (K39). Four writers, one file format: predictions
+another rate (K37), ``smooth_carla_animation`` smoothed along time (K39), ``root_motion_carla_animation`` with the root motion of
+its planted feet (K40). Four writers, one file format: predictions
 (``save_carla_animation``), keypoint clips through a LinearAE flow (``lift_carla_animation``, K32), mocap clips
 (``retarget_carla_animation``, K35) and keypoint clips through a flow that predicts 3-D locations (``ik_carla_animation``, K36).
 """
@@ -14,18 +15,20 @@ import numpy as np
 from pedestrians_video_2_carla_amd.walker_control.carla_pose import BONE_NAMES, export_clips
 
 
-def save_carla_animation(path: str, outputs, fps: float = 30.0, out_fps=None, smooth=None) -> str:
+def save_carla_animation(path: str, outputs, fps: float = 30.0, out_fps=None, smooth=None, root_motion=None) -> str:
     """``outputs``: the list ``Trainer.predict`` returns, ``(sliced, meta)`` per batch. Every batch is converted with one
     ``carla_pose_export`` call and copied to the host once. Returns the path written (``.npz`` appended when missing).
     ``out_fps`` (here and in the other writers): every clip is resampled from ``fps`` to that rate where its rows are, before the
     copy (``ops.resample_carla_rows``, K37 on the device), and the file's ``fps`` is ``out_fps``. ``smooth`` (here and in the other
     writers): a ``CarlaSmoother`` or a dict of its arguments (``mode`` among them; ``one_euro`` takes ``fps`` from here when it has
     none); every clip is smoothed as a video of its own where its rows are (K39 on the device), at the source rate and before
-    the resampling. None: the file is what it is without the argument."""
+    the resampling. None: the file is what it is without the argument. ``root_motion`` (here and in the other writers): True, a
+    ``CarlaRootMotion`` or a dict of its arguments (``ground``); every clip, a video of its own, gets root rows that keep its
+    supporting foot planted (K40 on the device), after the smoothing and before the resampling. None: the bytes of before."""
     outputs = list(outputs)
     if not outputs:
         raise ValueError('no predictions to save')
-    resample = _stages(fps, out_fps, smooth)
+    resample = _stages(fps, out_fps, smooth, root_motion)
     rows = []
     for sliced, meta in outputs:
         b, r = export_clips(sliced, resample)
@@ -43,26 +46,40 @@ def _resampler(fps, out_fps):
     return CarlaResampler(fps, out_fps).resample
 
 
-def _stages(fps, out_fps, smooth):
-    """What happens to a batch's rows where they are: smoothing at the source rate, then resampling; None when neither is asked."""
+def _stages(fps, out_fps, smooth, root_motion=None):
+    """What happens to a batch's rows where they are: smoothing at the source rate, then the root motion of the planted feet,
+    then resampling; None when none of them is asked."""
     from pedestrians_video_2_carla_amd.walker_control.smooth import as_smoother
     smoother, resample = as_smoother(smooth, fps), _resampler(fps, out_fps)
-    if smoother is None:
-        return resample
-    if resample is None:
-        return smoother.smooth
-    return lambda bones, root: resample(*smoother.smooth(bones, root))
+    stages = [smoother.smooth] if smoother is not None else []
+    if root_motion is not None:
+        from pedestrians_video_2_carla_amd.walker_control.root_motion import as_root_motion
+        mover = as_root_motion(root_motion)
+        if mover is not None:
+            stages.append(mover.apply)
+    if resample is not None:
+        stages.append(resample)
+    if not stages:
+        return None
+    if len(stages) == 1:
+        return stages[0]
+
+    def run(bones, root):
+        for stage in stages:
+            bones, root = stage(bones, root)
+        return bones, root
+    return run
 
 
-def lift_carla_animation(path: str, flow, batches, fps: float = 30.0, out_fps=None, smooth=None) -> str:
+def lift_carla_animation(path: str, flow, batches, fps: float = 30.0, out_fps=None, smooth=None, root_motion=None) -> str:
     """The file ``save_carla_animation(path, trainer.predict(flow, batches), fps)`` writes, from ``Trainer.predict_carla``:
     a LinearAE flow takes one launch per batch (K32) and no pose tensor is materialised; bones and root travel to the host
     together, one copy per batch. ``batches``: ``(frames, targets, meta)`` as for ``predict``."""
     from pedestrians_video_2_carla_amd.trainer import Trainer
-    return _write_device_rows(path, Trainer().predict_carla(flow, batches), fps, 'no predictions to save', out_fps, smooth)
+    return _write_device_rows(path, Trainer().predict_carla(flow, batches), fps, 'no predictions to save', out_fps, smooth, root_motion)
 
 
-def retarget_carla_animation(path: str, batches, fps: float = 30.0, device=None, out_fps=None, smooth=None) -> str:
+def retarget_carla_animation(path: str, batches, fps: float = 30.0, device=None, out_fps=None, smooth=None, root_motion=None) -> str:
     """Mocap clips as the file ``save_carla_animation`` writes: ``batches`` of ``(frames, targets, meta)`` whose targets hold
     ``amass_body_pose`` (B,T,66) -- the stored AMASS subsets, a mixture's AMASS clips -- and ``world_rot`` (B,T,3,3) where the
     subset has it (the identity otherwise; the root location of a body pose is zero). One ``ops.smpl_to_carla`` call per batch
@@ -75,23 +92,25 @@ def retarget_carla_animation(path: str, batches, fps: float = 30.0, device=None,
             if 'amass_body_pose' not in targets:
                 raise KeyError('amass_body_pose is missing from the targets: not a batch of AMASS clips')
             yield (*retargeter.export(targets['amass_body_pose'], meta, targets.get('world_rot')), meta)
-    return _write_device_rows(path, clips(), fps, 'no clips to save', out_fps, smooth)
+    return _write_device_rows(path, clips(), fps, 'no clips to save', out_fps, smooth, root_motion)
 
 
-def ik_carla_animation(path: str, flow, batches, fps: float = 30.0, out_fps=None, smooth=None) -> str:
+def ik_carla_animation(path: str, flow, batches, fps: float = 30.0, out_fps=None, smooth=None, root_motion=None) -> str:
     """The file of ``save_carla_animation`` from a flow whose movements model outputs absolute locations (PoseFormer,
     Baseline3DPose, ``--movements_output_type absolute_loc``): ``Trainer.predict_carla(flow, batches, ik=True)`` fits the bone
     rotations to the predicted locations with one launch of K36 per batch; bones and root travel to the host together, one copy
     per batch. ``batches``: ``(frames, targets, meta)`` as for ``predict``."""
     from pedestrians_video_2_carla_amd.trainer import Trainer
-    return _write_device_rows(path, Trainer().predict_carla(flow, batches, ik=True), fps, 'no predictions to save', out_fps, smooth)
+    return _write_device_rows(path, Trainer().predict_carla(flow, batches, ik=True), fps, 'no predictions to save', out_fps, smooth,
+                              root_motion)
 
 
-def _write_device_rows(path: str, batches, fps: float, when_empty: str, out_fps=None, smooth=None) -> str:
+def _write_device_rows(path: str, batches, fps: float, when_empty: str, out_fps=None, smooth=None, root_motion=None) -> str:
     """``batches`` of (bones (n,T,J,6), root (n,T,6), meta) on the device: bones and root travel to the host together, one copy
-    per batch, smoothed (``smooth``) and then resampled to ``out_fps`` before it when those are given."""
+    per batch, smoothed (``smooth``), given root motion (``root_motion``) and then resampled to ``out_fps`` before it when those
+    are given."""
     import torch
-    resample = _stages(fps, out_fps, smooth)
+    resample = _stages(fps, out_fps, smooth, root_motion)
     rows = []
     for bones, root, meta in batches:
         if resample is not None:
@@ -161,6 +180,27 @@ def smooth_carla_animation(src_path: str, dst_path: str, mode: str = 'gaussian',
         pieces.append(smoother.flush())
         out_b, out_r = torch.cat([p[0] for p in pieces], 1), torch.cat([p[1] for p in pieces], 1)
     both = torch.cat((out_b, out_r.unsqueeze(-2)), -2).cpu().numpy()
+    return _write(dst_path, [(both[..., :-1, :], both[..., -1, :], {'age': src['age'], 'gender': src['gender']})], src['fps'])
+
+
+def root_motion_carla_animation(src_path: str, dst_path: str, ground=None, chunk=None, device=None) -> str:
+    """The file at ``src_path`` with root rows that keep every clip's supporting foot planted (``CarlaRootMotion(ground)``; on
+    ``device``, K40 there for a GPU), everything else as stored; a stored root that already moves is honoured. ``chunk``: the
+    clips stream through ``push`` in pieces of that many frames, as a video that arrives piece by piece would; the file is
+    the same. Returns the path written."""
+    import torch
+    from pedestrians_video_2_carla_amd.walker_control.root_motion import CarlaRootMotion
+    src = load_carla_animation(src_path)
+    mover = CarlaRootMotion(ground)
+    bones, root = (torch.from_numpy(src[k]).to(device) if device is not None else torch.from_numpy(src[k]) for k in ('bones', 'root'))
+    if chunk is None:
+        out_r = mover.apply(bones, root)[1]
+    else:
+        if int(chunk) < 1:
+            raise ValueError(f'root_motion_carla_animation: chunk = {chunk}; at least one frame expected')
+        out_r = torch.cat([mover.push(bones[:, t:t + int(chunk)], root[:, t:t + int(chunk)])[1]
+                           for t in range(0, bones.shape[1], int(chunk))], 1)
+    both = torch.cat((bones, out_r.unsqueeze(-2)), -2).cpu().numpy()
     return _write(dst_path, [(both[..., :-1, :], both[..., -1, :], {'age': src['age'], 'gender': src['gender']})], src['fps'])
 
 

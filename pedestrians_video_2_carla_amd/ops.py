@@ -3822,6 +3822,64 @@ def smooth_carla_rows(bones: Tensor, root: Optional[Tensor] = None, *, mode: str
     return out_b, out_r, None
 
 
+# ---- K40: root motion of CARLA rows from their planted feet (csrc/p2c_root_motion.hip) -----------------------------------------
+def root_motion_framework() -> bool:
+    """P2C_ROOT_MOTION_FRAMEWORK=1: ``root_motion_carla_rows`` runs its tensor definition on the device (the comparison arm of
+    tools/bench_root_motion.py)."""
+    return os.environ.get('P2C_ROOT_MOTION_FRAMEWORK', '0') == '1'
+
+
+def root_motion_tile() -> int:
+    """Frames of a tile of K40: the length at which a video takes more than one pass of the scan."""
+    return int(_lib.lib().p2c_carla_root_motion_tile())
+
+
+@torch.no_grad()
+def root_motion_carla_rows(bones: Tensor, root: Optional[Tensor] = None, *, ground=None, state=None, first_frame: int = 0,
+                           want: Sequence[str] = ('root',), mapping=None, max_blocks: int = 0) -> Dict[str, object]:
+    """Root rows that keep the supporting foot planted (definition: ``walker_control/root_motion.py``). ``bones`` (N,T,26,6) and
+    ``root`` (N,T,6) or None (all-zero root rows), rows of (x, y, z, pitch, yaw, roll) -> a dict with the ``want``-ed among
+    ``root`` (N,T,6: x and y moved by the running sum of the steps, z put on ``ground`` when that is given, the angles bit for
+    bit), ``steps`` (N,T,2) int32 in quanta of 2^-10 of the length unit and ``contact`` (N,T) int8 (0..3 = foot R, toe R, foot L,
+    toe L; -1 where a frame pair had a non-finite value), and always ``state`` = ``(S (N,2) int64, points (N,4,3))`` after the
+    last frame. ``bones[:, 0]`` is global frame ``first_frame``; ``first_frame > 0`` continues a video and needs the ``state`` the
+    call before returned (``CarlaRootMotion.push`` keeps it; with ``first_frame = 0`` a state is not read). Each clip is a video
+    of its own. The CARLA skeleton is the only tree: another J raises. Views are made contiguous; nothing is recorded for
+    autograd. fp32 device tensors outside autocast take K40; host tensors, fp64, other dtypes and
+    ``P2C_ROOT_MOTION_FRAMEWORK=1`` take the tensor definition. ``mapping``: None / 'auto' chooses by size between 'per_video' (1:
+    a workgroup per video, one launch) and 'frame_parallel' (2: two launches over (video, tile)); all give the same bits.
+    ``max_blocks`` lowers the kernels' grid cap (tests)."""
+    from pedestrians_video_2_carla_amd.walker_control import root_motion as rm
+    rm.check_bones(bones, root)
+    want, mapping_id, z0, first_frame = rm.check_want(want), rm.check_mapping(mapping), rm.check_ground(ground), int(first_frame)
+    state = rm.check_state(bones, state, first_frame)
+    N, T = bones.shape[:2]
+    given = [t for t in (bones, root, state[1] if state is not None else None) if t is not None]   # the int64 offset is on their device
+    if T == 0 or not _carla_kernel_ok(*given) or root_motion_framework():
+        full = rm.root_motion_rows(bones, root, z0, state, first_frame)
+        return {**{k: full[k] for k in want}, 'state': full['state']}
+    lib = _lib.lib()
+    src_b, src_r = (t.detach().contiguous() if t is not None else None for t in (bones, root))
+    in_s, in_p = (t.detach().contiguous() for t in state) if state is not None and first_frame > 0 else (None, None)
+    dev = bones.device
+    out_root = torch.empty((N, T, 6), dtype=torch.float32, device=dev)
+    steps = torch.empty((N, T, 2), dtype=torch.int32, device=dev) if 'steps' in want else None
+    contact = torch.empty((N, T), dtype=torch.int8, device=dev) if 'contact' in want else None
+    new_s, new_p = torch.empty((N, 2), dtype=torch.int64, device=dev), torch.empty((N, 4, 3), dtype=torch.float32, device=dev)
+    if N > 0:
+        ws_bytes = int(lib.p2c_carla_root_motion_workspace(N, T, mapping_id))
+        if ws_bytes < 0:
+            raise _lib.P2CError(f'root_motion_carla_rows: {N} videos of {T} frames are more than K40 takes')
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if ws_bytes else None
+        with torch.cuda.device(dev):
+            _lib.check(lib.p2c_carla_root_motion_fwd(src_b.data_ptr(), _ptr(src_r), _ptr(in_s), _ptr(in_p), out_root.data_ptr(),
+                                                     _ptr(steps), _ptr(contact), new_s.data_ptr(), new_p.data_ptr(), N, T,
+                                                     first_frame, 0.0 if z0 is None else z0, int(z0 is not None), mapping_id,
+                                                     int(max_blocks), _ptr(ws), _stream()), 'p2c_carla_root_motion_fwd')
+    out = {'root': out_root, 'steps': steps, 'contact': contact}
+    return {**{k: out[k] for k in want}, 'state': (new_s, new_p)}
+
+
 # ---- K33: decoded video clips -> the pose-estimation flow's input frames (csrc/p2c_frames.hip) ---------------------------------
 FRAMES_MAX_TARGET = 1024             # the largest target size K33 is dispatched for
 

@@ -829,7 +829,8 @@ class Trainer:
         finally:
             flow.train(was_training)
 
-    def predict_carla(self, flow, batches: Iterable, ik: bool = False, src_fps=None, out_fps=None, smooth=None) -> List:
+    def predict_carla(self, flow, batches: Iterable, ik: bool = False, src_fps=None, out_fps=None, smooth=None,
+                      root_motion=None) -> List:
         """The predict loop for a CARLA player: per batch ``(bones (B,T,26,6), root (B,T,6), meta)``, the rows
         ``export_clips(flow.predict_step(batch))`` would give, left on the batch's device. A LinearAE flow takes one launch per
         batch (K32, ``walker_control.carla_lifter.CarlaLifter``); other movements models the composed path. A movements model
@@ -839,8 +840,10 @@ class Trainer:
         clip's rows are resampled from the one rate to the other where they are (``CarlaResampler.resample``, K37: one more
         launch per batch), so T becomes the clip's output count. ``smooth``: a ``CarlaSmoother`` or a dict of its arguments; every
         clip's rows are smoothed along time as a video of its own (``CarlaSmoother.smooth``, K39: one more launch per batch)
-        before any resampling (a dict for ``one_euro`` without ``fps`` takes ``src_fps``). Eval mode, no gradients, the flow's train / eval mode is
-        put back afterwards."""
+        before any resampling (a dict for ``one_euro`` without ``fps`` takes ``src_fps``). ``root_motion``: True, a
+        ``CarlaRootMotion`` or a dict of its arguments; every clip, a video of its own, gets root rows that keep its supporting
+        foot planted (``CarlaRootMotion.apply``, K40: one more launch per batch), after the smoothing and before any resampling.
+        Eval mode, no gradients, the flow's train / eval mode is put back afterwards."""
         from pedestrians_video_2_carla_amd.walker_control.carla_lifter import CarlaLifter
         if (src_fps is None) != (out_fps is None):
             raise ValueError('predict_carla: src_fps and out_fps come together or not at all')
@@ -849,6 +852,11 @@ class Trainer:
         else:
             from pedestrians_video_2_carla_amd.walker_control.resample import CarlaResampler
             rate = CarlaResampler(src_fps, out_fps).resample
+        if root_motion is not None:
+            from pedestrians_video_2_carla_amd.walker_control.root_motion import as_root_motion
+            mover, after = as_root_motion(root_motion), rate
+            if mover is not None:
+                rate = lambda bones, root: after(*mover.apply(bones, root))            # noqa: E731
         if smooth is not None:
             from pedestrians_video_2_carla_amd.walker_control.smooth import as_smoother
             smoother, resample = as_smoother(smooth, src_fps), rate
