@@ -1335,6 +1335,56 @@ P2C_API int p2c_carla_root_motion_fwd(const float *bones, const float *root, con
                                       int64_t first_frame, double ground, int32_t has_ground, int32_t mapping,
                                       int32_t max_blocks, void *workspace, void *stream);
 
+/* ---- K41: a CARLA animation as a loop: cycle search and seam blend (csrc/p2c_loop.hip) ---------------------------------------
+ * The exported rows are as long as the clip that went in; a scenario needs a walker that keeps walking. Replaying the rows jumps
+ * at the seam and, after K40, snaps the root back. This stage finds the cycle that closes best and plays it for any number of
+ * frames; the reference has no such step. Definition: walker_control/loop.py. fp32, no backward. q[t, j] is the unit quaternion
+ * of bone row (t, j) as p2c_carla_resample_fwd forms it.
+ *
+ * p2c_carla_loop_find_fwd: the search, per video.
+ *   bones (N,T,J,6); weights (J) finite and >= 0 on the device, or NULL for ones. The root is not read.
+ *   d(a, b) = sum_j w_j (1 - <q[a,j], q[b,j]>^2), j ascending, the four products of a dot product added from the first to the last.
+ *   C(s, e) = sum_{k = -blend .. 0} d(s + k, e + k), k ascending, where blend <= s, s + min_period <= e <= s + max_period and
+ *   e <= T - 1 (an admissible pair); +inf elsewhere.
+ *   out_loop (N,2) int64, out_loop_cost (N): the admissible pair with the smallest finite cost, ties to the smallest s, then the
+ *     smallest e, and its cost; (-1, -1) and NaN when no admissible pair has a finite cost.
+ *   out_cost (N,T,T) or NULL: every C(s, e). What is written to an output does not depend on the others.
+ *   workspace  p2c_carla_loop_find_workspace(N, T, J, blend) bytes on the device, 8-byte aligned: one 64-bit word a video, set and
+ *     read back by the same call (-1: sizes the entry point refuses).
+ * A workgroup takes a (video, 32 x 32 tile of (s, e)); a tile off the band min_period <= e - s <= max_period is skipped. The
+ * quaternions of the tile's 2 (32 + blend) frames are formed once into LDS, the (32 + blend)^2 tile of d there, and each lane sums
+ * its pairs' diagonals in ascending k; at most 64 KB, the bones in chunks when they do not fit. The video's minimum is an integer
+ * atomic minimum on an order-preserving 64-bit key (the cost's bits, then s, then e): exact, independent of the order of arrival.
+ * No floating-point atomics. C(s, e) is the work of one lane in a fixed order: its bits do not depend on the grid, on max_blocks,
+ * on whether out_cost is asked for or on the batch around the video. A NaN row poisons the entries whose window reads it.
+ *
+ * p2c_carla_loop_play_fwd: the chosen cycles played, one lane per output row.
+ *   bones (N,T,J,6), root (N,T,6) or NULL; loop (N,2) int64 on the device; out_bones (N,frames,J,6), out_root (N,frames,6) or NULL:
+ *     outputs first_output .. first_output + frames - 1.
+ *   Output g of a video with loop (s, e), P = e - s: c = g div P, phi = g mod P, a = s + phi. phi < P - blend: row a copied bit for
+ *   bit. Otherwise u = (float)((phi - (P - blend) + 1) / (double)(blend + 1)), b = a - P, and the row is the interpolation of
+ *   p2c_carla_resample_fwd of rows a and b at u. Root x and y in fp64: delta = root[e] - root[s]; m = root[a] outside the window,
+ *   (1 - u) root[a] + u (root[b] + delta) inside; out = (float)(m + c delta), every product and sum rounded on its own; cycle 0
+ *   outside the window is copied. A video whose loop is not blend <= s < e <= T - 1 -- (-1, -1) among them -- plays NaN rows; no
+ *   loop is followed outside the video. An output depends on g alone: pieces give the bits of one call. No LDS, no atomics.
+ *
+ * max_blocks  0: the kernels' own grid cap; > 0 lowers it (workgroups stride over tiles, lanes over rows).
+ * In this order, before anything is launched: P2C_E_SHAPE for negative sizes or first_output, max_blocks < 0, J outside
+ * [1, P2C_LOOP_MAX_J], blend outside [0, P2C_LOOP_MAX_BLEND], T > P2C_LOOP_MAX_T, N T (J + 1) or N frames (J + 1) >= 2^31,
+ * first_output > 2^40; the search: T < 2, min_period < 1, max_period < min_period; the player: T < 2 with outputs asked for;
+ * P2C_E_NULL for a missing bones, loop, out_loop, out_loop_cost or out_bones, root without out_root or the reverse, a missing
+ * workspace. Then N = 0 or frames = 0: nothing is launched. */
+#define P2C_LOOP_MAX_BLEND 32
+#define P2C_LOOP_MAX_J 64
+#define P2C_LOOP_MAX_T 16384
+P2C_API int64_t p2c_carla_loop_find_workspace(int64_t N, int64_t T, int32_t J, int32_t blend);
+P2C_API int p2c_carla_loop_find_fwd(const float *bones, const float *weights, int64_t *out_loop, float *out_loop_cost,
+                                    float *out_cost, int64_t N, int64_t T, int32_t J, int32_t blend, int64_t min_period,
+                                    int64_t max_period, int32_t max_blocks, void *workspace, void *stream);
+P2C_API int p2c_carla_loop_play_fwd(const float *bones, const float *root, const int64_t *loop, float *out_bones,
+                                    float *out_root, int64_t N, int64_t T, int32_t J, int64_t frames, int64_t first_output,
+                                    int32_t blend, int32_t max_blocks, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

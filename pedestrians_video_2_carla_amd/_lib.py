@@ -380,11 +380,15 @@ SYMBOLS = {
     'p2c_carla_root_motion_tile': (_i32, []),
     'p2c_carla_root_motion_workspace': (_i64, [_i64, _i64, _i32]),
     'p2c_carla_root_motion_fwd': (ctypes.c_int, [_vp] * 9 + [_i64, _i64, _i64, ctypes.c_double, _i32, _i32, _i32, _vp, _vp]),
+    'p2c_carla_loop_find_workspace': (_i64, [_i64, _i64, _i32, _i32]),
+    'p2c_carla_loop_find_fwd': (ctypes.c_int, [_vp] * 5 + [_i64, _i64, _i32, _i32, _i64, _i64, _i32, _vp, _vp]),
+    'p2c_carla_loop_play_fwd': (ctypes.c_int, [_vp] * 5 + [_i64, _i64, _i32, _i64, _i64, _i32, _i32, _vp]),
 }
 
 P2C_ROOT_MOTION_MAPPING = {'auto': 0, 'per_video': 1, 'frame_parallel': 2}
 
 P2C_SMOOTH_MAX_RADIUS = 32
+P2C_LOOP_MAX_BLEND, P2C_LOOP_MAX_J, P2C_LOOP_MAX_T = 32, 64, 16384
 
 P2C_GENERATE_NOISE = {'zero': 0, 'uniform': 1}
 P2C_GENERATE_MAPPING = {'auto': 0, 'sequential': 1, 'frame_parallel': 2}

@@ -3880,6 +3880,101 @@ def root_motion_carla_rows(bones: Tensor, root: Optional[Tensor] = None, *, grou
     return {**{k: out[k] for k in want}, 'state': (new_s, new_p)}
 
 
+# ---- K41: CARLA rows as a loop: cycle search and seam blend (csrc/p2c_loop.hip) ------------------------------------------------
+def loop_framework() -> bool:
+    """P2C_LOOP_FRAMEWORK=1: ``find_carla_loop`` and ``loop_carla_rows`` run their tensor definitions on the device (the
+    comparison arm of tools/bench_loop.py)."""
+    return os.environ.get('P2C_LOOP_FRAMEWORK', '0') == '1'
+
+
+def _loop_kernel_ok(bones: Tensor, frames: int, *more: Optional[Tensor]) -> bool:
+    """K41's domain: fp32 on the device outside autocast, 1 <= J <= 64, 2 <= T <= 16 384, row counts under 2^31."""
+    from pedestrians_video_2_carla_amd.walker_control import loop as lp
+    N, T, n_joints, _ = bones.shape
+    return (_carla_kernel_ok(bones, *(t for t in more if t is not None)) and not loop_framework()
+            and 1 <= n_joints <= lp.MAX_J and 2 <= T <= lp.MAX_T
+            and N * max(T, frames) * (n_joints + 1) < 2 ** 31)
+
+
+@torch.no_grad()
+def find_carla_loop(bones: Tensor, *, blend, min_period, max_period=None, weights=None, want: Sequence[str] = ('loop',),
+                    max_blocks: int = 0) -> Dict[str, Tensor]:
+    """The cycle of every video that closes best (definition: ``walker_control/loop.py``). ``bones`` (N,T,J,6), rows of (x, y, z,
+    pitch, yaw, roll) -> a dict with ``loop`` (N,2) int64, the pair ``(s, e)``: frames ``s .. e - 1`` and then ``s`` again, and
+    ``loop_cost`` (N), its cost; with ``'cost'`` in ``want`` also ``cost`` (N,T,T), every pair's. The cost of a pair compares the
+    ``blend`` frames that lead into ``s`` and ``s`` itself with those that lead into ``e`` and ``e``, bone by bone, as
+    ``weights[j] sin^2`` of half the angle between the two rotations (``weights`` (J) finite and >= 0, default ones); pairs with
+    ``blend <= s``, ``s + min_period <= e <= s + max_period`` (default T) and ``e <= T - 1`` are admissible, the others cost
+    ``+inf``. The smallest finite cost wins, ties to the smallest ``s``, then the smallest ``e``; a video without one gets ``(-1,
+    -1)`` and NaN. What is returned for a key does not depend on what else is asked for. Views are made contiguous; nothing is
+    recorded for autograd. fp32 device tensors outside autocast with J <= 64 and 2 <= T <= 16 384 take K41; host tensors, fp64,
+    other dtypes and sizes and ``P2C_LOOP_FRAMEWORK=1`` take the tensor definition. ``max_blocks`` lowers the kernel's grid cap
+    (tests)."""
+    from pedestrians_video_2_carla_amd.walker_control import loop as lp, resample as rs
+    blend = lp.check_blend(blend)
+    min_period, max_period = lp.check_periods(min_period, max_period)
+    want = lp.check_want(want)
+    rs.check_rows(bones, None, None, 'find_carla_loop')
+    w = lp.check_weights(weights, bones)
+    N, T, n_joints, _ = bones.shape
+    if not _loop_kernel_ok(bones, 0, w):
+        full = lp.find_loop(bones, blend, min_period, max_period, w)
+        return {k: full[k] for k in ('loop', 'loop_cost') + (('cost',) if 'cost' in want else ())}
+    lib = _lib.lib()
+    dev = bones.device
+    src, w = bones.detach().contiguous(), (w.contiguous() if w is not None else None)
+    loop = torch.empty((N, 2), dtype=torch.int64, device=dev)
+    loop_cost = torch.empty((N,), dtype=torch.float32, device=dev)
+    cost = torch.empty((N, T, T), dtype=torch.float32, device=dev) if 'cost' in want else None
+    if N > 0:
+        ws_bytes = int(lib.p2c_carla_loop_find_workspace(N, T, n_joints, blend))
+        if ws_bytes < 0:
+            raise _lib.P2CError(f'find_carla_loop: {N} videos of {T} frames are more than K41 takes')
+        ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.p2c_carla_loop_find_fwd(src.data_ptr(), _ptr(w), loop.data_ptr(), loop_cost.data_ptr(), _ptr(cost), N, T,
+                                                   n_joints, blend, min(min_period, lp.INT_MAX),
+                                                   lp.INT_MAX if max_period is None else min(max_period, lp.INT_MAX),
+                                                   int(max_blocks), ws.data_ptr(), _stream()), 'p2c_carla_loop_find_fwd')
+    out = {'loop': loop, 'loop_cost': loop_cost}
+    if cost is not None:
+        out['cost'] = cost
+    return out
+
+
+@torch.no_grad()
+def loop_carla_rows(bones: Tensor, root: Optional[Tensor] = None, *, loop, blend, frames, first_output: int = 0,
+                    max_blocks: int = 0) -> Tuple[Tensor, Optional[Tensor]]:
+    """The cycles ``find_carla_loop`` chose, played (definition: ``walker_control/loop.py``). ``bones`` (N,T,J,6) and ``root``
+    (N,T,6) or None, ``loop`` (N,2) whole numbers -> ``(bones (N,frames,J,6), root (N,frames,6) or None)``: outputs
+    ``first_output .. first_output + frames - 1`` of an animation that plays frames ``s .. e - 1`` over and over. Outside the last
+    ``blend`` frames of a cycle the source rows are copied bit for bit; inside them they are blended (K37's interpolation)
+    towards the frames that lead into ``s``, so that the cycle closes. Root x and y advance by ``root[e] - root[s]`` a cycle, as
+    a product formed in fp64: an output depends on its index alone and pieces give the bits of one call. A video with ``loop =
+    (-1, -1)`` plays NaN rows; another pair that is not ``blend <= s < e <= T - 1`` raises. Views are made contiguous; nothing
+    is recorded for autograd. fp32 device tensors outside autocast with J <= 64 and 2 <= T <= 16 384 take K41 (one launch for
+    bones and root); host tensors, fp64, other dtypes and sizes and ``P2C_LOOP_FRAMEWORK=1`` take the tensor definition.
+    ``max_blocks`` lowers the kernel's grid cap (tests)."""
+    from pedestrians_video_2_carla_amd.walker_control import loop as lp, resample as rs
+    blend, frames = lp.check_blend(blend), lp.check_frames(frames)
+    first_output = int(first_output)
+    if first_output < 0:
+        raise ValueError(f'loop_carla_rows: first_output = {first_output}; not negative expected')
+    rs.check_rows(bones, root, None, 'loop_carla_rows')
+    pairs = lp.check_loop(loop, bones, blend)
+    N, T, n_joints, _ = bones.shape
+    if N == 0 or frames == 0 or first_output + frames > 2 ** 40 or not _loop_kernel_ok(bones, frames, root):
+        return lp.play_rows(bones, root, pairs, blend, frames, first_output)
+    src_b, src_r = (t.detach().contiguous() if t is not None else None for t in (bones, root))
+    out_b = torch.empty((N, frames, n_joints, 6), dtype=torch.float32, device=bones.device)
+    out_r = torch.empty((N, frames, 6), dtype=torch.float32, device=bones.device) if root is not None else None
+    with torch.cuda.device(bones.device):
+        _lib.check(_lib.lib().p2c_carla_loop_play_fwd(src_b.data_ptr(), _ptr(src_r), pairs.contiguous().data_ptr(), out_b.data_ptr(),
+                                                      _ptr(out_r), N, T, n_joints, frames, first_output, blend, int(max_blocks),
+                                                      _stream()), 'p2c_carla_loop_play_fwd')
+    return out_b, out_r
+
+
 # ---- K33: decoded video clips -> the pose-estimation flow's input frames (csrc/p2c_frames.hip) ---------------------------------
 FRAMES_MAX_TARGET = 1024             # the largest target size K33 is dispatched for
 

@@ -830,7 +830,7 @@ class Trainer:
             flow.train(was_training)
 
     def predict_carla(self, flow, batches: Iterable, ik: bool = False, src_fps=None, out_fps=None, smooth=None,
-                      root_motion=None) -> List:
+                      root_motion=None, loop=None) -> List:
         """The predict loop for a CARLA player: per batch ``(bones (B,T,26,6), root (B,T,6), meta)``, the rows
         ``export_clips(flow.predict_step(batch))`` would give, left on the batch's device. A LinearAE flow takes one launch per
         batch (K32, ``walker_control.carla_lifter.CarlaLifter``); other movements models the composed path. A movements model
@@ -843,6 +843,9 @@ class Trainer:
         before any resampling (a dict for ``one_euro`` without ``fps`` takes ``src_fps``). ``root_motion``: True, a
         ``CarlaRootMotion`` or a dict of its arguments; every clip, a video of its own, gets root rows that keep its supporting
         foot planted (``CarlaRootMotion.apply``, K40: one more launch per batch), after the smoothing and before any resampling.
+        ``loop``: a ``CarlaLooper`` that knows its ``frames`` or a dict of its arguments with ``frames``; every clip, a video of its
+        own, becomes that many frames of the cycle that closes best (``CarlaLooper.loop``, K41), after the root motion and before
+        any resampling, so T becomes ``frames``.
         Eval mode, no gradients, the flow's train / eval mode is put back afterwards."""
         from pedestrians_video_2_carla_amd.walker_control.carla_lifter import CarlaLifter
         if (src_fps is None) != (out_fps is None):
@@ -852,6 +855,10 @@ class Trainer:
         else:
             from pedestrians_video_2_carla_amd.walker_control.resample import CarlaResampler
             rate = CarlaResampler(src_fps, out_fps).resample
+        if loop is not None:
+            from pedestrians_video_2_carla_amd.walker_control.loop import as_looper
+            looper, then = as_looper(loop), rate
+            rate = lambda bones, root: then(*looper.loop(bones, root))                 # noqa: E731
         if root_motion is not None:
             from pedestrians_video_2_carla_amd.walker_control.root_motion import as_root_motion
             mover, after = as_root_motion(root_motion), rate
